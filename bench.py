@@ -10,12 +10,23 @@ Driver contract: `python bench.py --gpus N --steps K --warmup W`; under
 torchrun one rank per GPU (reads RANK/WORLD_SIZE/LOCAL_RANK).  Rank 0 prints
 one JSON line; `value` aggregates over all N GPUs; timing is max-over-ranks,
 bracketed by barrier + torch.cuda.synchronize on both sides.
+
+A plain run does only what the headline figure needs: set up, warm up, time
+`--steps` steps, print the result line.  `--dump-outputs DIR` additionally
+runs the timed path once more from the seeded initial state and writes what
+that step produced (see `dump_outputs`), so two builds can be compared
+output for output: data, labels and initial state are a pure function of
+the arguments.  `--full` is where any measurement beyond the headline figure
+goes; this benchmark has none, so today it changes nothing.
 """
 from __future__ import annotations
 
 import argparse
+import copy
+import glob
 import json
 import os
+import shutil
 import time
 
 import torch
@@ -44,7 +55,101 @@ def get_args():
     p.add_argument("--graph", type=int, default=0,
                    help="capture the train step in a hipGraph and replay "
                         "(single-GPU only)")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", dest="dump_outputs", default=None,
+                   metavar="DIR",
+                   help="after the timed steps, run one more step from the "
+                        "seeded initial state and write its results as "
+                        "DIR/<name>.npy (float32)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements that are not needed for "
+                        "the headline figure (none exist yet)")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if args.warmup < 0:
+        p.error("--warmup must not be negative")
+    return args
+
+
+FIND_DB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                           "benchmarks", "miopen_find_db")
+
+
+def seed_miopen_find_db():
+    """Copy the committed MIOpen find results for the default configuration
+    into the user find-db directory, unless a find-db of that name is there
+    already.  Without them the first step runs MIOpen's find over every conv
+    shape at batch 3x512, which takes minutes (naive solvers included) before
+    the first timed step; with them the first step only looks the solvers up.
+    The files are keyed by MIOpen version and arch, so another version simply
+    misses them and runs its own find as before."""
+    dst_dir = os.environ.get("MIOPEN_USER_DB_PATH") or \
+        os.path.join(os.path.expanduser("~"), ".config", "miopen")
+    for src in glob.glob(os.path.join(FIND_DB_DIR, "*.ufdb.txt")):
+        dst = os.path.join(dst_dir, os.path.basename(src))
+        if os.path.exists(dst):
+            continue
+        try:
+            os.makedirs(dst_dir, exist_ok=True)
+            tmp = f"{dst}.{os.getpid()}.tmp"
+            shutil.copyfile(src, tmp)
+            os.replace(tmp, dst)
+        except OSError:
+            pass  # read-only home: MIOpen runs its find as before
+
+
+# at most this many elements per dumped array (float32: 16 MiB)
+DUMP_SAMPLE = 4 * 1024 * 1024
+
+
+def restore_state(model, optimizer, model_state, optim_state):
+    """Put parameters, running statistics and optimizer state back to the
+    snapshot, in place (a captured graph keeps pointing at the same
+    storage)."""
+    model.load_state_dict(model_state)
+    if not optimizer.state:
+        # torch.optim delegate (CPU): its state lives behind load_state_dict
+        optimizer.load_state_dict(optim_state)
+        return
+    with torch.no_grad():
+        for p, st in optimizer.state.items():
+            if "momentum_buffer" in st:
+                st["momentum_buffer"].zero_()
+            if "master" in st:
+                st["master"].copy_(p)
+
+
+def dump_outputs(out_dir, model, last, rank):
+    """Write what a training step hands back to its caller: the two loss
+    terms, the parameters the optimizer step left behind, and the running
+    statistics (buffers) of every whitening/BN site.  Parameters and buffers
+    are each flattened in named order (every tensor in its logical index
+    order, as float32); beyond DUMP_SAMPLE elements a fixed seeded sample is
+    written, in ascending flat index.  Under 40 MB in all.  Under torchrun
+    every rank writes its own files."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "" if rank == 0 else f".rank{rank}"
+
+    def save(name, arr):
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), arr)
+
+    def flat_sample(named):
+        with torch.no_grad():
+            flat = torch.cat([t.detach().float().cpu().flatten()
+                              for _, t in named]).numpy()
+        if flat.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(
+                flat.size, size=DUMP_SAMPLE, replace=False))
+            flat = flat[idx]
+        return flat
+
+    save("losses", torch.stack([last["cls_loss"].float(),
+                                last["mec_loss"].float()]).cpu().numpy())
+    save("params", flat_sample(model.named_parameters()))
+    save("buffers", flat_sample((n, b) for n, b in model.named_buffers()
+                                if b.is_floating_point()))
 
 
 def main():
@@ -61,6 +166,8 @@ def main():
         os.environ.setdefault("MIOPEN_CACHE_DIR",
                               f"/tmp/miopen-cache-rank{local_rank}")
     use_cuda = torch.cuda.is_available() and args.device != "cpu"
+    if use_cuda:
+        seed_miopen_find_db()
     if args.device == "cpu":
         # keep the CPU smoke path fast
         args.batch = min(args.batch, 2)
@@ -105,6 +212,12 @@ def main():
         data = data.contiguous(memory_format=torch.channels_last)
     labels = torch.randint(0, args.num_classes, (b,), device=device)
 
+    last = {}  # what the most recent step produced (references only)
+    if args.dump_outputs:
+        # the dumped step starts from this seeded state, see below
+        model_state = {k: v.clone() for k, v in model.state_dict().items()}
+        optim_state = copy.deepcopy(optimizer.state_dict())
+
     def step():
         optimizer.zero_grad(set_to_none=True)
         out = model(data)
@@ -115,6 +228,7 @@ def main():
         if ddp.enabled:
             ddp.sync()
         optimizer.step()
+        last["cls_loss"], last["mec_loss"] = cls_loss.detach(), mec.detach()
 
     def barrier_sync():
         if world > 1:
@@ -151,6 +265,18 @@ def main():
                          device=device if use_cuda else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs:
+        # The state the timed steps leave behind is not reproducible: the
+        # reductions accumulate with atomics, their arrival order varies, and
+        # training a random-init bf16 net amplifies that from step to step.
+        # So the timed path runs once more, from the seeded initial state:
+        # its inputs are then identical in every run and its results differ
+        # only by that one step's rounding.
+        restore_state(model, optimizer, model_state, optim_state)
+        run_step()
+        barrier_sync()
+        dump_outputs(args.dump_outputs, model, last, rank)
 
     if rank == 0:
         total_images = n_per_gpu * world * args.steps
