@@ -90,7 +90,10 @@ class _HipWhitenMulti(torch.autograd.Function):
     slices of the same stacked tensors."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, running_means, running_vars, cfg):
+    def forward(ctx, x, gamma, beta, running_means, running_vars, cfg,
+                res=None):
+        # res (channels_last layout only; passed by _HipWhitenJoin, never
+        # through apply): the apply pass writes relu(norm(x) + res)
         ext = _ext()
         parts = cfg["parts"]
         g = x.shape[1] // cfg["num_groups"]
@@ -166,7 +169,11 @@ class _HipWhitenMulti(torch.autograd.Function):
             ext.matfn_ns_fwd(cov, wmat, ys, zs, svals, eps, ns_iters)
             saved_mat = (ys, zs, svals)
 
-        if layout == "cl":
+        if res is not None:
+            assert layout == "cl"
+            ext.whiten_apply_res_cl(x, mean, wmat, gflat, bflat, res, out, g,
+                                    c, m_count, True, has_affine, parts)
+        elif layout == "cl":
             ext.whiten_apply_cl(x, mean, wmat, gflat, bflat, out, g, c,
                                 m_count, relu, has_affine, parts)
         else:
@@ -194,7 +201,8 @@ class _HipWhitenMulti(torch.autograd.Function):
         ctx.cfg = cfg
         ctx.g = g
         ctx.layout = layout
-        ctx.m_count = ctx_count
+        ctx.m_count = ctx_count   # global positions per branch (for 1/m)
+        ctx.m_local = m_count     # this rank's rows per branch (kernel M)
         ctx.sync_world = world
         ctx.mean = mean
         ctx.wmat = wmat
@@ -207,6 +215,15 @@ class _HipWhitenMulti(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
+        dx, _, dgamma, dbeta = _HipWhitenMulti.run_backward(ctx, dout)
+        return dx, dgamma, dbeta, None, None, None
+
+    @staticmethod
+    def run_backward(ctx, dout, gb=None, join=False):
+        """Returns (dx, gid, dgamma, dbeta).  ``join``: ``dout``/``gb`` are
+        the two consumers' gradients of y = relu(norm(x) + identity) (gb may
+        be None); the join reduce writes gid = (dout + gb) * (y > 0), which
+        is the identity's gradient and the dout of the plain apply pass."""
         ext = _ext()
         cfg = ctx.cfg
         parts, relu, mode, eps = cfg["parts"], cfg["relu"], cfg["mode"], cfg["eps"]
@@ -228,14 +245,27 @@ class _HipWhitenMulti(torch.autograd.Function):
             dout = dout.contiguous()
         mean, wmat = ctx.mean, ctx.wmat
         m_count = ctx.m_count
+        # the kernels index x with the LOCAL per-branch row count; the global
+        # count (sync-stats mode) only enters through inv_m
+        m_local = ctx.m_local
 
         dgb = torch.zeros(parts, 2, c, device=dev, dtype=torch.float32)
         dW = torch.zeros(ng_all, g, g, device=dev, dtype=torch.float32)
         dx = torch.empty_like(x)
 
-        if layout == "cl":
+        gid = None
+        if join:
+            assert layout == "cl"
+            if gb is not None:
+                gb = gb.contiguous(memory_format=torch.channels_last)
+            gid = torch.empty_like(x)
+            ext.whiten_join_bwd_reduce_cl(x, out, dout, gb, mean, wmat,
+                                          ctx.gflat, gid, dW, dgb.reshape(-1),
+                                          g, c, m_local, ctx.has_affine, parts)
+            dout, relu = gid, False
+        elif layout == "cl":
             ext.whiten_bwd_reduce_cl(x, dout, mean, wmat, ctx.gflat, ctx.bflat,
-                                     dW, dgb.reshape(-1), g, c, m_count,
+                                     dW, dgb.reshape(-1), g, c, m_local,
                                      relu, ctx.has_affine, parts)
         else:
             for p in range(parts):
@@ -273,7 +303,7 @@ class _HipWhitenMulti(torch.autograd.Function):
 
         if layout == "cl":
             ext.whiten_bwd_apply_cl(x, dout, mean, wmat, ctx.gflat, ctx.bflat,
-                                    S, corr, dx, g, c, m_count, relu,
+                                    S, corr, dx, g, c, m_local, relu,
                                     ctx.has_affine, use_batch, parts)
         else:
             for p in range(parts):
@@ -291,7 +321,63 @@ class _HipWhitenMulti(torch.autograd.Function):
             dbeta = dgb[:, 1].sum(0).reshape(gamma.shape).to(gamma.dtype)
         else:
             dgamma = dbeta = None
-        return dx, dgamma, dbeta, None, None, None
+        return dx, gid, dgamma, dbeta
+
+
+class _HipWhitenJoin(torch.autograd.Function):
+    """y = relu(whiten(x) + identity) with the join fused into the apply
+    pass (forward) and into the reduce pass (backward); channels_last only.
+
+    Returns TWO outputs aliasing one buffer, one per consumer of a block
+    output (the next block's conv1 and its identity).  Backward then gets
+    the two gradients un-summed (either may be None) and adds them inside
+    the join reduce kernel — autograd never runs its accumulation kernel."""
+
+    @staticmethod
+    def forward(ctx, x, identity, gamma, beta, running_means, running_vars,
+                cfg):
+        ctx.set_materialize_grads(False)
+        res = identity.detach()  # channels_last: join_supported checked it
+        y = _HipWhitenMulti.forward(ctx, x, gamma, beta, running_means,
+                                    running_vars, cfg, res=res)
+        return y, y.view_as(y)
+
+    @staticmethod
+    def backward(ctx, ga, gb):
+        if ga is None and gb is None:
+            return (None,) * 7
+        if ga is None:
+            ga, gb = gb, None
+        dx, gid, dgamma, dbeta = _HipWhitenMulti.run_backward(
+            ctx, ga, gb, join=True)
+        return dx, gid, dgamma, dbeta, None, None, None
+
+
+def join_supported(kind, x, identity, cfg):
+    """True when the fused residual join serves this site: channels_last
+    fp32/bf16 in the NHWC kernels' (C, g) range, identity shaped and laid
+    out like x (an identity in another layout would need a hidden copy pass,
+    so such a site takes the unfused composition instead)."""
+    if x.dtype not in (torch.float32, torch.bfloat16) or x.dim() != 4:
+        return False
+    if identity.shape != x.shape or identity.dtype != x.dtype \
+            or identity.device != x.device \
+            or identity.stride() != x.stride():
+        return False
+    c = x.shape[1]
+    if kind == "whiten":
+        return _whiten_layout(x, c, c // cfg["num_groups"]) == "cl"
+    return _bn_layout(x, c) == "cl"
+
+
+def whiten_join(x, identity, gamma, beta, running_means, running_vars, cfg):
+    return _HipWhitenJoin.apply(x, identity, gamma, beta, running_means,
+                                running_vars, cfg)
+
+
+def batch_norm_join(x, identity, gamma, beta, running_means, running_vars, cfg):
+    return _HipBatchNormJoin.apply(x, identity, gamma, beta, running_means,
+                                   running_vars, cfg)
 
 
 def whiten_multi(x, gamma, beta, running_means, running_vars, cfg):
@@ -307,7 +393,9 @@ def whiten_multi(x, gamma, beta, running_means, running_vars, cfg):
 
 class _HipBatchNormMulti(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, gamma, beta, running_means, running_vars, cfg):
+    def forward(ctx, x, gamma, beta, running_means, running_vars, cfg,
+                res=None):
+        # res: as in _HipWhitenMulti.forward (passed by _HipBatchNormJoin)
         ext = _ext()
         parts = cfg["parts"]
         eps, momentum = cfg["eps"], cfg["momentum"]
@@ -381,7 +469,11 @@ class _HipBatchNormMulti(torch.autograd.Function):
                                for p in range(parts)]).reshape(-1)
             istd = torch.rsqrt(var + eps).contiguous()
 
-        if layout == "cl":
+        if res is not None:
+            assert layout == "cl" and x.dim() == 4
+            ext.bn_apply_res_cl(x, mean, istd, gflat, bflat, res, out, c, cnt,
+                                True, has_affine, parts)
+        elif layout == "cl":
             ext.bn_apply_cl(x, mean, istd, gflat, bflat, out, c, cnt, relu,
                             has_affine, parts)
         else:
@@ -407,6 +499,13 @@ class _HipBatchNormMulti(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
+        dx, _, dgamma, dbeta = _HipBatchNormMulti.run_backward(ctx, dout)
+        return dx, dgamma, dbeta, None, None, None
+
+    @staticmethod
+    def run_backward(ctx, dout, gb=None, join=False):
+        """Returns (dx, gid, dgamma, dbeta); ``join`` as in
+        _HipWhitenMulti.run_backward."""
         ext = _ext()
         cfg = ctx.cfg
         parts, relu = cfg["parts"], cfg["relu"]
@@ -424,10 +523,19 @@ class _HipBatchNormMulti(torch.autograd.Function):
         sums = torch.zeros(parts, 2, c, device=dev, dtype=torch.float32)
         dx = torch.empty_like(x)
         cnt_total = getattr(ctx, "cnt_total", ctx.cnt)
+        gid = None
         if layout == "cl":
-            ext.bn_bwd_reduce_cl(x, dout, mean, istd, ctx.gflat, ctx.bflat,
-                                 sums.reshape(-1), c, ctx.cnt, relu,
-                                 ctx.has_affine, parts)
+            if join:
+                if gb is not None:
+                    gb = gb.contiguous(memory_format=torch.channels_last)
+                gid = torch.empty_like(x)
+                ext.bn_join_bwd_reduce_cl(x, out, dout, gb, mean, istd, gid,
+                                          sums.reshape(-1), c, ctx.cnt, parts)
+                dout, relu = gid, False
+            else:
+                ext.bn_bwd_reduce_cl(x, dout, mean, istd, ctx.gflat, ctx.bflat,
+                                     sums.reshape(-1), c, ctx.cnt, relu,
+                                     ctx.has_affine, parts)
             apply_sums = sums
             if getattr(ctx, "sync_world", 1) > 1:
                 apply_sums = _allreduce(sums.clone())
@@ -460,7 +568,30 @@ class _HipBatchNormMulti(torch.autograd.Function):
             dbeta = sums[:, 0].sum(0).reshape(gamma.shape).to(gamma.dtype)
         else:
             dgamma = dbeta = None
-        return dx, dgamma, dbeta, None, None, None
+        return dx, gid, dgamma, dbeta
+
+
+class _HipBatchNormJoin(torch.autograd.Function):
+    """y = relu(bn(x) + identity); see _HipWhitenJoin."""
+
+    @staticmethod
+    def forward(ctx, x, identity, gamma, beta, running_means, running_vars,
+                cfg):
+        ctx.set_materialize_grads(False)
+        res = identity.detach()  # channels_last: join_supported checked it
+        y = _HipBatchNormMulti.forward(ctx, x, gamma, beta, running_means,
+                                       running_vars, cfg, res=res)
+        return y, y.view_as(y)
+
+    @staticmethod
+    def backward(ctx, ga, gb):
+        if ga is None and gb is None:
+            return (None,) * 7
+        if ga is None:
+            ga, gb = gb, None
+        dx, gid, dgamma, dbeta = _HipBatchNormMulti.run_backward(
+            ctx, ga, gb, join=True)
+        return dx, gid, dgamma, dbeta, None, None, None
 
 
 def batch_norm_multi(x, gamma, beta, running_means, running_vars, cfg):

@@ -1519,6 +1519,281 @@ __global__ void bn_bwd_apply_nhwc_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Residual join fused into a block's last norm site (NHWC).
+//
+// Forward:  out = relu?(norm(x) + res) — the add is done in fp32 and rounded
+// once on the store, so the norm output is never materialised.  These are
+// siblings of the plain apply kernels (which stay untouched: same code, same
+// register counts) with one extra streamed operand, offset per branch like x.
+//
+// Backward: g = (ga + gb) * (y > 0), rounded to T and stored to gid (it is
+// the identity's gradient and the dout of the unchanged *_bwd_apply pass),
+// while the reduce sums are accumulated from that ROUNDED value — exactly
+// what the plain reduce would read back.  gb may be null (one consumer).
+// Lane mapping, branch offsets and LDS/atomic epilogue are those of the
+// plain *_bwd_reduce_nhwc kernels.
+// ---------------------------------------------------------------------------
+
+template <typename T> DEV_INLINE float round_to(float v);
+template <> DEV_INLINE float round_to<float>(float v) { return v; }
+template <> DEV_INLINE float round_to<c10::BFloat16>(float v) {
+  // same round-to-nearest-even as f32x2_to_bf16 (the store is then exact)
+  union { unsigned int u; float f; } x;
+  x.f = v;
+  x.u = (x.u + 0x7fffu + ((x.u >> 16) & 1u)) & 0xffff0000u;
+  return x.f;
+}
+
+template <typename T, int G>
+__global__ void whiten_apply_res_nhwc_kernel(
+    const T* __restrict__ x, const T* __restrict__ res,
+    const float* __restrict__ mean,
+    const float* __restrict__ W, const T* __restrict__ gamma,
+    const T* __restrict__ beta, T* __restrict__ out,
+    int C, int64_t M, int relu, int has_affine) {
+  const int part = blockIdx.y;
+  x += (int64_t)part * M * C;
+  res += (int64_t)part * M * C;
+  out += (int64_t)part * M * C;
+  mean += (int64_t)part * C;
+  const int CW = C < 256 ? C : 256;
+  const int GW = CW / G;
+  const int c0 = blockIdx.z * 256 + (threadIdx.x % GW) * G;
+  const int grp = part * (C / G) + c0 / G;
+  const int rows_per_iter = blockDim.x / GW;
+  const int row_in_block = threadIdx.x / GW;
+
+  float m_[G], Wr[G][G], gm[G], bt[G];
+#pragma unroll
+  for (int i = 0; i < G; ++i) {
+    m_[i] = mean[c0 + i];
+    gm[i] = has_affine ? ldf(gamma + c0 + i) : 1.f;
+    bt[i] = has_affine ? ldf(beta + c0 + i) : 0.f;
+#pragma unroll
+    for (int j = 0; j < G; ++j) Wr[i][j] = W[((int64_t)grp * G + i) * G + j];
+  }
+  const int64_t stride = (int64_t)gridDim.x * rows_per_iter;
+  for (int64_t m = (int64_t)blockIdx.x * rows_per_iter + row_in_block; m < M;
+       m += stride) {
+    float v[G], r[G], y[G];
+    load_group<T, G>(x + m * C + c0, v);
+    load_group<T, G>(res + m * C + c0, r);
+#pragma unroll
+    for (int j = 0; j < G; ++j) v[j] -= m_[j];
+#pragma unroll
+    for (int i = 0; i < G; ++i) {
+      float a = 0.f;
+#pragma unroll
+      for (int j = 0; j < G; ++j) a += Wr[i][j] * v[j];
+      a = a * gm[i] + bt[i] + r[i];
+      y[i] = relu ? fmaxf(a, 0.f) : a;
+    }
+    store_group<T, G>(out + m * C + c0, y);
+  }
+}
+
+template <typename T>
+__global__ void bn_apply_res_nhwc_kernel(
+    const T* __restrict__ x, const T* __restrict__ res,
+    const float* __restrict__ mean,
+    const float* __restrict__ istd, const T* __restrict__ gamma,
+    const T* __restrict__ beta, T* __restrict__ out, int C, int64_t M,
+    int relu, int has_affine) {
+  const int part = blockIdx.y;
+  x += (int64_t)part * M * C;
+  res += (int64_t)part * M * C;
+  out += (int64_t)part * M * C;
+  mean += (int64_t)part * C;
+  istd += (int64_t)part * C;
+  constexpr int VC = 4;
+  const int CW = C < 1024 ? C : 1024;
+  const int NCH = CW / VC;
+  const int c0 = blockIdx.z * 1024 + (threadIdx.x % NCH) * VC;
+  const int rows_per_iter = blockDim.x / NCH;
+  const int row_in_block = threadIdx.x / NCH;
+  float mu[VC], is[VC], gm[VC], bt[VC];
+#pragma unroll
+  for (int k = 0; k < VC; ++k) {
+    mu[k] = mean[c0 + k];
+    is[k] = istd[c0 + k];
+    gm[k] = has_affine ? ldf(gamma + c0 + k) : 1.f;
+    bt[k] = has_affine ? ldf(beta + c0 + k) : 0.f;
+  }
+  const int64_t stride = (int64_t)gridDim.x * rows_per_iter;
+  for (int64_t m = (int64_t)blockIdx.x * rows_per_iter + row_in_block; m < M;
+       m += stride) {
+    float v[VC], r[VC];
+    load_group<T, VC>(x + m * C + c0, v);
+    load_group<T, VC>(res + m * C + c0, r);
+#pragma unroll
+    for (int k = 0; k < VC; ++k) {
+      const float y = (v[k] - mu[k]) * is[k] * gm[k] + bt[k] + r[k];
+      v[k] = relu ? fmaxf(y, 0.f) : y;
+    }
+    store_group<T, VC>(out + m * C + c0, v);
+  }
+}
+
+template <typename T, int G>
+__global__ void whiten_join_bwd_reduce_nhwc_kernel(
+    const T* __restrict__ x, const T* __restrict__ y,
+    const T* __restrict__ ga, const T* __restrict__ gb /* may be null */,
+    const float* __restrict__ mean, const float* __restrict__ W,
+    const T* __restrict__ gamma, T* __restrict__ gid,
+    float* __restrict__ dWacc, float* __restrict__ dgb,
+    int C, int64_t M, int has_affine) {
+  const int part = blockIdx.y;
+  const int64_t poff = (int64_t)part * M * C;
+  x += poff; y += poff; ga += poff; gid += poff;
+  if (gb) gb += poff;
+  mean += (int64_t)part * C;
+  dgb += (int64_t)part * 2 * C;
+  const int CW = C < 256 ? C : 256;
+  const int GW = CW / G;
+  const int c0 = blockIdx.z * 256 + (threadIdx.x % GW) * G;
+  const int grp = part * (C / G) + c0 / G;
+  const int rows_per_iter = blockDim.x / GW;
+  const int row_in_block = threadIdx.x / GW;
+
+  float m_[G], Wr[G][G], gm[G];
+#pragma unroll
+  for (int i = 0; i < G; ++i) {
+    m_[i] = mean[c0 + i];
+    gm[i] = has_affine ? ldf(gamma + c0 + i) : 1.f;
+#pragma unroll
+    for (int j = 0; j < G; ++j) Wr[i][j] = W[((int64_t)grp * G + i) * G + j];
+  }
+  float dWl[G][G], dg[G], db[G];
+#pragma unroll
+  for (int i = 0; i < G; ++i) {
+    dg[i] = 0.f; db[i] = 0.f;
+#pragma unroll
+    for (int j = 0; j < G; ++j) dWl[i][j] = 0.f;
+  }
+  const int64_t stride = (int64_t)gridDim.x * rows_per_iter;
+  for (int64_t m = (int64_t)blockIdx.x * rows_per_iter + row_in_block; m < M;
+       m += stride) {
+    const int64_t off = m * C + c0;
+    float xv[G], yv[G], dyv[G];
+    load_group<T, G>(x + off, xv);
+    load_group<T, G>(y + off, yv);
+    load_group<T, G>(ga + off, dyv);
+    if (gb) {
+      float t[G];
+      load_group<T, G>(gb + off, t);
+#pragma unroll
+      for (int j = 0; j < G; ++j) dyv[j] += t[j];
+    }
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+      dyv[j] = yv[j] > 0.f ? round_to<T>(dyv[j]) : 0.f;
+      xv[j] -= m_[j];
+    }
+    store_group<T, G>(gid + off, dyv);
+#pragma unroll
+    for (int i = 0; i < G; ++i) {
+      float y0 = 0.f;
+#pragma unroll
+      for (int j = 0; j < G; ++j) y0 += Wr[i][j] * xv[j];
+      const float dy = dyv[i];
+      db[i] += dy;
+      dg[i] += dy * y0;
+      const float dy0 = dy * gm[i];
+#pragma unroll
+      for (int j = 0; j < G; ++j) dWl[i][j] += dy0 * xv[j];
+    }
+  }
+  constexpr int NV = 2 * G + G * G;
+  __shared__ float lacc[(256 / G) * NV];  // [GW][NV], GW <= 256/G
+  float* mine = lacc + (threadIdx.x % GW) * NV;
+  for (int k = threadIdx.x; k < GW * NV; k += blockDim.x) lacc[k] = 0.f;
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < G; ++i) {
+    atomicAdd(&mine[i], dg[i]);
+    atomicAdd(&mine[G + i], db[i]);
+#pragma unroll
+    for (int j = 0; j < G; ++j) atomicAdd(&mine[2 * G + i * G + j], dWl[i][j]);
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < GW * NV; k += blockDim.x) {
+    const int lg = k / NV;
+    const int kk = k % NV;
+    const int lgidx = blockIdx.z * (256 / G) + lg;      // group within part
+    const int gidx = part * (C / G) + lgidx;            // global group
+    const int cg0 = lgidx * G;
+    if (kk < G) atomicAdd(&dgb[cg0 + kk], lacc[k]);
+    else if (kk < 2 * G) atomicAdd(&dgb[C + cg0 + (kk - G)], lacc[k]);
+    else atomicAdd(&dWacc[(int64_t)gidx * G * G + (kk - 2 * G)], lacc[k]);
+  }
+}
+
+template <typename T>
+__global__ void bn_join_bwd_reduce_nhwc_kernel(
+    const T* __restrict__ x, const T* __restrict__ y,
+    const T* __restrict__ ga, const T* __restrict__ gb /* may be null */,
+    const float* __restrict__ mean, const float* __restrict__ istd,
+    T* __restrict__ gid, float* __restrict__ sums, int C, int64_t M) {
+  const int part = blockIdx.y;
+  const int64_t poff = (int64_t)part * M * C;
+  x += poff; y += poff; ga += poff; gid += poff;
+  if (gb) gb += poff;
+  mean += (int64_t)part * C;
+  istd += (int64_t)part * C;
+  sums += (int64_t)part * 2 * C;
+  constexpr int VC = 4;
+  const int CW = C < 1024 ? C : 1024;
+  const int NCH = CW / VC;
+  const int c0 = blockIdx.z * 1024 + (threadIdx.x % NCH) * VC;
+  const int rows_per_iter = blockDim.x / NCH;
+  const int row_in_block = threadIdx.x / NCH;
+  float s_dy[VC], s_dyxh[VC], mu[VC], is[VC];
+#pragma unroll
+  for (int k = 0; k < VC; ++k) {
+    s_dy[k] = 0.f; s_dyxh[k] = 0.f;
+    mu[k] = mean[c0 + k];
+    is[k] = istd[c0 + k];
+  }
+  const int64_t stride = (int64_t)gridDim.x * rows_per_iter;
+  for (int64_t m = (int64_t)blockIdx.x * rows_per_iter + row_in_block; m < M;
+       m += stride) {
+    const int64_t off = m * C + c0;
+    float xv[VC], yv[VC], dv[VC];
+    load_group<T, VC>(x + off, xv);
+    load_group<T, VC>(y + off, yv);
+    load_group<T, VC>(ga + off, dv);
+    if (gb) {
+      float t[VC];
+      load_group<T, VC>(gb + off, t);
+#pragma unroll
+      for (int k = 0; k < VC; ++k) dv[k] += t[k];
+    }
+#pragma unroll
+    for (int k = 0; k < VC; ++k) {
+      dv[k] = yv[k] > 0.f ? round_to<T>(dv[k]) : 0.f;
+      const float xh = (xv[k] - mu[k]) * is[k];
+      s_dy[k] += dv[k];
+      s_dyxh[k] += dv[k] * xh;
+    }
+    store_group<T, VC>(gid + off, dv);
+  }
+  __shared__ float lacc[2 * 1024];
+  const int cb = c0 - blockIdx.z * 1024;
+  for (int k = threadIdx.x; k < 2 * CW; k += blockDim.x) lacc[k] = 0.f;
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < VC; ++k) {
+    atomicAdd(&lacc[cb + k], s_dy[k]);
+    atomicAdd(&lacc[CW + cb + k], s_dyxh[k]);
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < CW; k += blockDim.x) {
+    atomicAdd(&sums[blockIdx.z * 1024 + k], lacc[k]);
+    atomicAdd(&sums[C + blockIdx.z * 1024 + k], lacc[CW + k]);
+  }
+}
+
 // ===========================================================================
 // Domain BatchNorm
 // ===========================================================================
@@ -2445,6 +2720,135 @@ void bn_bwd_apply_cl(Tensor x, Tensor dout, Tensor mean,
   });
 }
 
+// ---- residual join fused into the last norm site (see the kernels) ----
+// res / gb are optional: without res the plain apply kernel runs (bit-
+// identical to *_apply_cl); without gb the join has a single consumer.
+// Group sizes 2 and 4 only — the NHWC route never takes g=8 (it spills).
+
+#define DWT_SWITCH_G24(g, body)                                                \
+  switch (g) {                                                                 \
+    case 2: { constexpr int G = 2; body; break; }                              \
+    case 4: { constexpr int G = 4; body; break; }                              \
+    default: TORCH_CHECK(false, "join kernels: unsupported group size ", g);   \
+  }
+
+void whiten_apply_res_cl(Tensor x, Tensor mean, Tensor W, Tensor gamma,
+                         Tensor beta, c10::optional<Tensor> res, Tensor out,
+                         int64_t g, int64_t C, int64_t M, bool relu,
+                         bool has_affine, int64_t parts) {
+  if (!res.has_value()) {
+    whiten_apply_cl(x, mean, W, gamma, beta, out, g, C, M, relu, has_affine,
+                    parts);
+    return;
+  }
+  TORCH_CHECK(res->scalar_type() == x.scalar_type() &&
+              res->numel() == x.numel(), "whiten_apply_res_cl: res mismatch");
+  const int zslices = (C + 255) / 256;
+  DISPATCH_FT(x, "whiten_apply_res_cl", [&] {
+    DWT_SWITCH_G24(g, {
+      const int GW = (C < 256 ? C : 256) / G;
+      dim3 grid(nhwc_elem_blocks(M, 256 / GW, zslices * parts), parts, zslices);
+      hipLaunchKernelGGL((dwt::whiten_apply_res_nhwc_kernel<scalar_t, G>), grid,
+                         dim3(256), 0, cur_stream(), x.data_ptr<scalar_t>(),
+                         res->data_ptr<scalar_t>(),
+                         mean.data_ptr<float>(), W.data_ptr<float>(),
+                         has_affine ? gamma.data_ptr<scalar_t>() : nullptr,
+                         has_affine ? beta.data_ptr<scalar_t>() : nullptr,
+                         out.data_ptr<scalar_t>(), (int)C, M, relu ? 1 : 0,
+                         has_affine ? 1 : 0);
+    });
+  });
+}
+
+void bn_apply_res_cl(Tensor x, Tensor mean, Tensor istd, Tensor gamma,
+                     Tensor beta, c10::optional<Tensor> res, Tensor out,
+                     int64_t C, int64_t M, bool relu, bool has_affine,
+                     int64_t parts) {
+  if (!res.has_value()) {
+    bn_apply_cl(x, mean, istd, gamma, beta, out, C, M, relu, has_affine, parts);
+    return;
+  }
+  TORCH_CHECK(res->scalar_type() == x.scalar_type() &&
+              res->numel() == x.numel(), "bn_apply_res_cl: res mismatch");
+  const int zslices = (C + 1023) / 1024;
+  DISPATCH_FT(x, "bn_apply_res_cl", [&] {
+    const int NCH = (C < 1024 ? C : 1024) / 4;
+    const int rpi = std::max(256 / NCH, 1);
+    dim3 grid(nhwc_elem_blocks(M, rpi, zslices * parts), parts, zslices);
+    hipLaunchKernelGGL((dwt::bn_apply_res_nhwc_kernel<scalar_t>), grid,
+                       dim3(256), 0, cur_stream(), x.data_ptr<scalar_t>(),
+                       res->data_ptr<scalar_t>(),
+                       mean.data_ptr<float>(), istd.data_ptr<float>(),
+                       has_affine ? gamma.data_ptr<scalar_t>() : nullptr,
+                       has_affine ? beta.data_ptr<scalar_t>() : nullptr,
+                       out.data_ptr<scalar_t>(), (int)C, M, relu ? 1 : 0,
+                       has_affine ? 1 : 0);
+  });
+}
+
+void whiten_join_bwd_reduce_cl(Tensor x, Tensor y, Tensor ga,
+                               c10::optional<Tensor> gb, Tensor mean, Tensor W,
+                               Tensor gamma, Tensor gid, Tensor dWacc,
+                               Tensor dgb, int64_t g, int64_t C, int64_t M,
+                               bool has_affine, int64_t parts) {
+  const int64_t numel = parts * M * C;
+  TORCH_CHECK(x.numel() == numel && y.numel() == numel &&
+              ga.numel() == numel && gid.numel() == numel &&
+              (!gb.has_value() || gb->numel() == numel),
+              "whiten_join_bwd_reduce_cl: size mismatch");
+  TORCH_CHECK(y.scalar_type() == x.scalar_type() &&
+              ga.scalar_type() == x.scalar_type() &&
+              gid.scalar_type() == x.scalar_type() &&
+              (!gb.has_value() || gb->scalar_type() == x.scalar_type()),
+              "whiten_join_bwd_reduce_cl: dtype mismatch");
+  const int zslices = (C + 255) / 256;
+  DISPATCH_FT(x, "whiten_join_bwd_reduce_cl", [&] {
+    DWT_SWITCH_G24(g, {
+      const int GW = (C < 256 ? C : 256) / G;
+      dim3 grid(nhwc_reduce_blocks(M, 256 / GW, zslices * parts), parts,
+                zslices);
+      hipLaunchKernelGGL((dwt::whiten_join_bwd_reduce_nhwc_kernel<scalar_t, G>),
+                         grid, dim3(256), 0, cur_stream(),
+                         x.data_ptr<scalar_t>(), y.data_ptr<scalar_t>(),
+                         ga.data_ptr<scalar_t>(),
+                         gb.has_value() ? gb->data_ptr<scalar_t>() : nullptr,
+                         mean.data_ptr<float>(), W.data_ptr<float>(),
+                         has_affine ? gamma.data_ptr<scalar_t>() : nullptr,
+                         gid.data_ptr<scalar_t>(), dWacc.data_ptr<float>(),
+                         dgb.data_ptr<float>(), (int)C, M, has_affine ? 1 : 0);
+    });
+  });
+}
+
+void bn_join_bwd_reduce_cl(Tensor x, Tensor y, Tensor ga,
+                           c10::optional<Tensor> gb, Tensor mean, Tensor istd,
+                           Tensor gid, Tensor sums, int64_t C, int64_t M,
+                           int64_t parts) {
+  const int64_t numel = parts * M * C;
+  TORCH_CHECK(x.numel() == numel && y.numel() == numel &&
+              ga.numel() == numel && gid.numel() == numel &&
+              (!gb.has_value() || gb->numel() == numel),
+              "bn_join_bwd_reduce_cl: size mismatch");
+  TORCH_CHECK(y.scalar_type() == x.scalar_type() &&
+              ga.scalar_type() == x.scalar_type() &&
+              gid.scalar_type() == x.scalar_type() &&
+              (!gb.has_value() || gb->scalar_type() == x.scalar_type()),
+              "bn_join_bwd_reduce_cl: dtype mismatch");
+  const int zslices = (C + 1023) / 1024;
+  DISPATCH_FT(x, "bn_join_bwd_reduce_cl", [&] {
+    const int NCH = (C < 1024 ? C : 1024) / 4;
+    dim3 grid(nhwc_reduce_blocks(M, 256 / NCH > 0 ? 256 / NCH : 1,
+                                 zslices * parts), parts, zslices);
+    hipLaunchKernelGGL((dwt::bn_join_bwd_reduce_nhwc_kernel<scalar_t>), grid,
+                       dim3(256), 0, cur_stream(), x.data_ptr<scalar_t>(),
+                       y.data_ptr<scalar_t>(), ga.data_ptr<scalar_t>(),
+                       gb.has_value() ? gb->data_ptr<scalar_t>() : nullptr,
+                       mean.data_ptr<float>(), istd.data_ptr<float>(),
+                       gid.data_ptr<scalar_t>(), sums.data_ptr<float>(), (int)C,
+                       M);
+  });
+}
+
 void matfn_chol_fwd(Tensor cov, Tensor W, Tensor L, double eps) {
   const int n_groups = cov.size(0);
   const int g = cov.size(1);
@@ -3007,6 +3411,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_apply_cl", &bn_apply_cl);
   m.def("bn_bwd_reduce_cl", &bn_bwd_reduce_cl);
   m.def("bn_bwd_apply_cl", &bn_bwd_apply_cl);
+  m.def("whiten_apply_res_cl", &whiten_apply_res_cl);
+  m.def("bn_apply_res_cl", &bn_apply_res_cl);
+  m.def("whiten_join_bwd_reduce_cl", &whiten_join_bwd_reduce_cl);
+  m.def("bn_join_bwd_reduce_cl", &bn_join_bwd_reduce_cl);
   m.def("matfn_chol_fwd", &matfn_chol_fwd);
   m.def("matfn_chol_bwd", &matfn_chol_bwd);
   m.def("matfn_ns_fwd", &matfn_ns_fwd);

@@ -25,7 +25,6 @@ import torch.nn as nn
 
 from ..ops.batch_norm import DomainBatchNorm2d
 from ..ops.whitening import WhiteningScaleShift
-from ..ops.functional import add_relu
 from ..ops.pooling import MaxPool2dDWT, global_avg_pool
 from .sites import norm_site
 
@@ -124,8 +123,21 @@ class Bottleneck(nn.Module):
                         planes * self.expansion, bn_dict, dpre)
 
     def forward(self, x):
+        return self.forward_pair(x, x)[0]
+
+    def forward_pair(self, x_main, x_id):
+        """Block forward on a block-input pair; returns the output pair.
+
+        ``x_main`` and ``x_id`` hold the same values (the two elements a
+        previous block's join returned, or one tensor twice): ``x_main``
+        feeds conv1 and the downsample conv, ``x_id`` is the identity when
+        there is no downsample.  Keeping the two uses on separate autograd
+        edges lets the previous join sum their gradients in its own backward
+        kernel.  The returned ``(y_a, y_b)`` are the next block's pair.
+        """
         tr = self.training
-        identity = x
+        x = x_main
+        identity = x_id
 
         out = self.conv1(x)
         out = norm_site(out, [self.bns1, self.bnt1, self.bnt1_aug],
@@ -134,8 +146,6 @@ class Bottleneck(nn.Module):
         out = norm_site(out, [self.bns2, self.bnt2, self.bnt2_aug],
                         self.gamma2, self.beta2, training=tr, relu=True)
         out = self.conv3(out)
-        out = norm_site(out, [self.bns3, self.bnt3, self.bnt3_aug],
-                        self.gamma3, self.beta3, training=tr, relu=False)
 
         if self.downsample is not None:
             identity = self.downsample(x)
@@ -144,7 +154,20 @@ class Bottleneck(nn.Module):
                 [self.downsample_bns, self.downsample_bnt, self.downsample_bnt_aug],
                 self.downsample_gamma, self.downsample_beta, training=tr, relu=False)
 
-        return add_relu(out, identity)
+        return norm_site(out, [self.bns3, self.bnt3, self.bnt3_aug],
+                         self.gamma3, self.beta3, training=tr, relu=True,
+                         residual=identity)
+
+
+class _Stage(nn.Sequential):
+    """A stage's blocks; threads each block's output pair into the next block
+    and hands out a single tensor (see Bottleneck.forward_pair)."""
+
+    def forward(self, x):
+        a = b = x
+        for block in self:
+            a, b = block.forward_pair(a, b)
+        return a
 
 
 class ResNetDWT(nn.Module):
@@ -187,7 +210,7 @@ class ResNetDWT(nn.Module):
         for i in range(1, blocks):
             layers.append(block(self.inplanes, planes, layer, i, bn_dict,
                                 group_size, whiten_mode=self.whiten_mode))
-        return nn.Sequential(*layers)
+        return _Stage(*layers)
 
     def forward(self, x):
         x = self.conv1(x)

@@ -34,14 +34,21 @@ def norm_site(
     training: bool,
     relu: bool,
     eval_branch: int = 1,
-) -> torch.Tensor:
+    residual: Optional[torch.Tensor] = None,
+):
     """Apply a multi-domain norm site.
 
     Training: batch is split into len(branches) equal streams, stream i
     normalized by branches[i].  Eval: the whole batch goes through
     ``branches[eval_branch]`` (the reference always evaluates with the target
     branch — SURVEY quirk #12).
+
+    With ``residual`` the site is a bottleneck exit: the result is the pair
+    ``(y_a, y_b)`` of ``Fdwt.norm_join``, both ``relu(norm(x) + residual)``
+    (``relu`` must be True — it follows the add), one per consumer.
     """
+    if residual is not None:
+        assert relu, "a residual join applies its ReLU after the add"
     first = branches[0]
     if training:
         use = list(branches)
@@ -53,13 +60,15 @@ def norm_site(
     if isinstance(first, (WhiteningScaleShift, WTransform2d)):
         whs = [_wh_of(b) for b in use]
         w0 = whs[0]
-        return Fdwt.whiten_multi(
-            x, gamma, beta,
-            [w.running_mean for w in whs],
-            [w.running_variance for w in whs],
-            parts=parts, num_groups=w0.num_groups, eps=w0.eps,
-            momentum=w0.momentum, training=training, mode=w0.mode, relu=relu,
-            track_running_stats=w0.track_running_stats)
+        kw = dict(parts=parts, num_groups=w0.num_groups, eps=w0.eps,
+                  momentum=w0.momentum, training=training, mode=w0.mode,
+                  track_running_stats=w0.track_running_stats)
+        rms = [w.running_mean for w in whs]
+        rvs = [w.running_variance for w in whs]
+        if residual is not None:
+            return Fdwt.norm_join("whiten", x, residual, gamma, beta, rms, rvs,
+                                  **kw)
+        return Fdwt.whiten_multi(x, gamma, beta, rms, rvs, relu=relu, **kw)
 
     if isinstance(first, (_DomainBatchNorm, nn.modules.batchnorm._BatchNorm)):
         momentum = first.momentum if first.momentum is not None else 0.0
@@ -71,13 +80,15 @@ def norm_site(
                 momentum = 1.0 / first.num_batches_tracked.item()
         spatial = x.dim() == 4
         gshape = (-1, 1, 1) if spatial else (1, -1)
-        return Fdwt.batch_norm_multi(
-            x,
-            gamma.reshape(gshape) if gamma is not None else None,
-            beta.reshape(gshape) if beta is not None else None,
-            [b.running_mean for b in use] if first.track_running_stats else None,
-            [b.running_var for b in use] if first.track_running_stats else None,
-            parts=parts, eps=first.eps, momentum=momentum, training=training,
-            relu=relu, track_running_stats=first.track_running_stats)
+        gamma = gamma.reshape(gshape) if gamma is not None else None
+        beta = beta.reshape(gshape) if beta is not None else None
+        rms = [b.running_mean for b in use] if first.track_running_stats else None
+        rvs = [b.running_var for b in use] if first.track_running_stats else None
+        kw = dict(parts=parts, eps=first.eps, momentum=momentum,
+                  training=training,
+                  track_running_stats=first.track_running_stats)
+        if residual is not None:
+            return Fdwt.norm_join("bn", x, residual, gamma, beta, rms, rvs, **kw)
+        return Fdwt.batch_norm_multi(x, gamma, beta, rms, rvs, relu=relu, **kw)
 
     raise TypeError(f"unsupported norm branch type {type(first)}")

@@ -312,6 +312,29 @@ class WhitenMulti(torch.autograd.Function):
         return dx, dgamma, dbeta, None, None, None
 
 
+def _whiten_cfg(
+    *,
+    parts: int,
+    num_groups: int,
+    eps: float = 1e-3,
+    momentum: float = 0.1,
+    training: bool = True,
+    mode: str = "chol",
+    relu: bool = False,
+    ns_iters: int = 7,
+    track_running_stats: bool = True,
+) -> dict:
+    cfg = dict(parts=parts, num_groups=num_groups, eps=eps, momentum=momentum,
+               training=training, mode=mode, relu=relu, ns_iters=ns_iters,
+               track_running_stats=track_running_stats)
+    if os.environ.get("DWT_AMD_STATS_SYNC") == "1":
+        # cross-rank batch statistics ('sync' stats mode, SURVEY §2.3):
+        # on GPU the HIP kernels serve it with a partial-sums -> all-reduce
+        # -> finalize split; torch path elsewhere
+        cfg["stats_sync"] = True
+    return cfg
+
+
 def whiten_multi(
     x: torch.Tensor,
     gamma: Optional[torch.Tensor],
@@ -329,14 +352,10 @@ def whiten_multi(
     ns_iters: int = 7,
     track_running_stats: bool = True,
 ) -> torch.Tensor:
-    cfg = dict(parts=parts, num_groups=num_groups, eps=eps, momentum=momentum,
-               training=training, mode=mode, relu=relu, ns_iters=ns_iters,
-               track_running_stats=track_running_stats)
-    if os.environ.get("DWT_AMD_STATS_SYNC") == "1":
-        # cross-rank batch statistics ('sync' stats mode, SURVEY §2.3):
-        # on GPU the HIP kernels serve it with a partial-sums -> all-reduce
-        # -> finalize split; torch path elsewhere
-        cfg["stats_sync"] = True
+    cfg = _whiten_cfg(parts=parts, num_groups=num_groups, eps=eps,
+                      momentum=momentum, training=training, mode=mode,
+                      relu=relu, ns_iters=ns_iters,
+                      track_running_stats=track_running_stats)
     if x.is_cuda:
         from ..kernels import dispatch
         if dispatch.available():
@@ -471,6 +490,22 @@ class BatchNormMulti(torch.autograd.Function):
         return dx, dgamma, dbeta, None, None, None
 
 
+def _bn_cfg(
+    *,
+    parts: int,
+    eps: float = 1e-5,
+    momentum: float = 0.1,
+    training: bool = True,
+    relu: bool = False,
+    track_running_stats: bool = True,
+) -> dict:
+    cfg = dict(parts=parts, eps=eps, momentum=momentum, training=training,
+               relu=relu, track_running_stats=track_running_stats)
+    if os.environ.get("DWT_AMD_STATS_SYNC") == "1":
+        cfg["stats_sync"] = True
+    return cfg
+
+
 def batch_norm_multi(
     x: torch.Tensor,
     gamma: Optional[torch.Tensor],
@@ -485,10 +520,8 @@ def batch_norm_multi(
     relu: bool = False,
     track_running_stats: bool = True,
 ) -> torch.Tensor:
-    cfg = dict(parts=parts, eps=eps, momentum=momentum, training=training,
-               relu=relu, track_running_stats=track_running_stats)
-    if os.environ.get("DWT_AMD_STATS_SYNC") == "1":
-        cfg["stats_sync"] = True
+    cfg = _bn_cfg(parts=parts, eps=eps, momentum=momentum, training=training,
+                  relu=relu, track_running_stats=track_running_stats)
     if x.is_cuda:
         from ..kernels import dispatch
         if dispatch.available():
@@ -620,6 +653,53 @@ class AddReluFn(torch.autograd.Function):
 
 def add_relu(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return AddReluFn.apply(a, b)
+
+
+def fused_join_enabled() -> bool:
+    """``DWT_AMD_FUSED_JOIN=0`` turns the fused residual join off (the A/B
+    switch for profiling and parity tests).  Read on every call."""
+    return os.environ.get("DWT_AMD_FUSED_JOIN", "1") != "0"
+
+
+def norm_join(
+    kind: str,
+    x: torch.Tensor,
+    identity: torch.Tensor,
+    gamma: Optional[torch.Tensor],
+    beta: Optional[torch.Tensor],
+    running_means: Optional[Sequence[torch.Tensor]],
+    running_vars: Optional[Sequence[torch.Tensor]],
+    **kw,
+):
+    """Bottleneck exit ``y = relu(norm(x) + identity)`` as a pair ``(y_a, y_b)``.
+
+    ``kind`` is ``"whiten"`` or ``"bn"``; ``kw`` are the keyword arguments of
+    :func:`whiten_multi` / :func:`batch_norm_multi` (``relu`` is implied).
+
+    Both elements hold the same values; hand one to each consumer of the
+    block output.  On the fused path (HIP extension, channels_last, fp32/bf16,
+    whitening group size 2 or 4) they are two autograd outputs aliasing ONE
+    buffer: the join is folded into the norm's apply pass, and the backward
+    receives the consumers' gradients separately and sums them inside its
+    reduce kernel.  Everywhere else this is ``add_relu(norm(x), identity)``
+    returned twice, and autograd sums the gradients as usual.
+    """
+    assert kind in ("whiten", "bn"), kind
+    kw = dict(kw, relu=False)
+    if x.is_cuda and fused_join_enabled():
+        from ..kernels import dispatch
+        if dispatch.available():
+            from ..kernels import hip_ops
+            cfg = _whiten_cfg(**kw) if kind == "whiten" else _bn_cfg(**kw)
+            if hip_ops.join_supported(kind, x, identity, cfg):
+                fn = hip_ops.whiten_join if kind == "whiten" \
+                    else hip_ops.batch_norm_join
+                return fn(x, identity, gamma, beta, running_means,
+                          running_vars, cfg)
+    multi = whiten_multi if kind == "whiten" else batch_norm_multi
+    y = add_relu(multi(x, gamma, beta, running_means, running_vars, **kw),
+                 identity)
+    return y, y
 
 
 def ce_loss(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
