@@ -27,6 +27,13 @@ R50_SHAPES = [
     ("l3.conv3", 192, 256, 14, 14, 1024, 1, 1, 0),
     ("l4.conv2", 192, 512, 14, 14, 512, 3, 2, 1),
     ("l4.conv3", 192, 512, 7, 7, 2048, 1, 1, 0),
+    # the remaining 1x1 stride-1 shapes (conv1 of later blocks / stage entry)
+    ("l1.conv1b", 192, 256, 56, 56, 64, 1, 1, 0),
+    ("l2.conv1b", 192, 512, 28, 28, 128, 1, 1, 0),
+    ("l3.conv1", 192, 512, 28, 28, 256, 1, 1, 0),
+    ("l3.conv1b", 192, 1024, 14, 14, 256, 1, 1, 0),
+    ("l4.conv1", 192, 1024, 14, 14, 512, 1, 1, 0),
+    ("l4.conv1b", 192, 2048, 7, 7, 512, 1, 1, 0),
 ]
 
 GEMM_SHAPES = [
@@ -34,6 +41,113 @@ GEMM_SHAPES = [
     ("sq2048", 2048, 2048, 2048),
     ("sq4096", 4096, 4096, 4096),
 ]
+
+
+# every 1x1 stride-1 forward conv of the backbone with the norm site behind
+# it: (name, Cin, H=W, Cout, norm kind)
+STATS_SHAPES = [
+    ("l1.conv1", 64, 56, 64, "whiten"),
+    ("l1.conv1b", 256, 56, 64, "whiten"),
+    ("l1.conv3/ds", 64, 56, 256, "whiten"),
+    ("l2.conv1", 256, 56, 128, "bn"),
+    ("l2.conv1b", 512, 28, 128, "bn"),
+    ("l2.conv3", 128, 28, 512, "bn"),
+    ("l3.conv1", 512, 28, 256, "bn"),
+    ("l3.conv1b", 1024, 14, 256, "bn"),
+    ("l3.conv3", 256, 14, 1024, "bn"),
+    ("l4.conv1", 1024, 14, 512, "bn"),
+    ("l4.conv1b", 2048, 7, 512, "bn"),
+    ("l4.conv3", 512, 7, 2048, "bn"),
+]
+
+
+def stats_mode(args):
+    """Per shape: library forward, the stand-alone stats kernel on its
+    output, our forward with the generic epilogue, and the fused forward +
+    stats kernel (dwt_amd.ops.mfma.conv1x1_stats).  `old/new` isolates the
+    wide-store epilogue plus the stats cost; `(lib+stats)/new` is what
+    routing a shape gains."""
+    from dwt_amd.kernels import dispatch
+    from dwt_amd.ops.mfma import (conv2d_fwd, conv_stats_shape_ok,
+                                  stats_acc_numel)
+    ext = dispatch.ext()
+    dev = torch.device("cuda:0")
+    n, parts, g = args.batch, 3, 4
+    lines = [f"# 1x1 conv forward + norm statistics, N={n} (bf16, NHWC, "
+             f"{parts} branches)",
+             "",
+             "ms per call; `stats` = accumulator zeroing + partial + finalize "
+             "kernels on the conv output; `fused` = zeroing + fused conv + "
+             "finalize kernel; `ours old` = our forward with the generic "
+             "epilogue, no statistics; `gain` = (lib fwd + stats) / fused; "
+             "`routed` is `conv_stats_shape_ok` (gain > 1.05 routes).",
+             "",
+             "| shape | M x Cout x Cin | lib fwd | stats | ours old | fused | "
+             "old/fused | gain | fused GB/s | routed |",
+             "|---|---|---|---|---|---|---|---|---|---|"]
+    only = [t for t in args.only.split(",") if t]
+    for name, cin, hw, cout, kind in STATS_SHAPES:
+        if only and not any(t in name for t in only):
+            continue
+        x = torch.randn(n, cin, hw, hw, device=dev).to(torch.bfloat16) \
+            .contiguous(memory_format=torch.channels_last)
+        wt = (torch.randn(cout, cin, 1, 1, device=dev) * 0.05).to(torch.bfloat16)
+        w2 = wt.reshape(cout, cin).contiguous()
+        m = n * hw * hw
+        mp = m // parts
+        out = torch.empty(n, cout, hw, hw, device=dev, dtype=torch.bfloat16,
+                          memory_format=torch.channels_last)
+        nacc = stats_acc_numel(kind, cout, parts, g)
+        kid = 0 if kind == "bn" else 1
+
+        def lib_fn():
+            return F.conv2d(x, wt)
+
+        # both sides as the step runs them: the old path's stats launch is the
+        # partial + finalize pair, the fused conv is followed by the finalize
+        mean = torch.empty(parts * cout, device=dev, dtype=torch.float32)
+        istd, var_unb = torch.empty_like(mean), torch.empty_like(mean)
+        ng_all = parts * cout // g
+        cov = torch.empty(ng_all, g, g, device=dev, dtype=torch.float32)
+
+        def final(acc):
+            if kind == "bn":
+                ext.bn_stats_final(acc, mean, istd, var_unb, cout, parts, mp,
+                                   1e-5)
+            else:
+                ext.whiten_stats_final(acc, mean, cov, g, ng_all, mp)
+
+        def stats_fn():
+            acc = torch.zeros(nacc, device=dev, dtype=torch.float32)
+            if kind == "bn":
+                ext.bn_stats_cl(out, acc, mean, istd, var_unb, cout, mp, 1e-5,
+                                parts)
+            else:
+                ext.whiten_stats_cl(out, acc, mean, cov, g, cout, mp, parts)
+
+        def old_fn():
+            return conv2d_fwd(x, wt)
+
+        def new_fn():
+            acc = torch.zeros(nacc, device=dev, dtype=torch.float32)
+            ext.conv1x1_stats(x, w2, out, acc, kid, g, parts, 0)
+            final(acc)
+
+        t_lib = timeit(lib_fn, args.iters)
+        t_old = timeit(old_fn, args.iters)
+        t_new = timeit(new_fn, args.iters)   # leaves `out` filled for stats
+        t_st = timeit(stats_fn, args.iters)
+        gbs = 2.0 * m * (cin + cout) / t_new / 1e9
+        lines.append(
+            f"| {name} ({kind}) | {m}x{cout}x{cin} | {t_lib*1e3:.3f} | "
+            f"{t_st*1e3:.3f} | {t_old*1e3:.3f} | {t_new*1e3:.3f} | "
+            f"{t_old/t_new:.2f}x | {(t_lib+t_st)/t_new:.2f}x | {gbs:.0f} | "
+            f"{'yes' if conv_stats_shape_ok(m, cin, cout) else 'no'} |")
+        print(lines[-1], flush=True)
+        del x, out
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print(f"wrote {args.out}")
 
 
 def timeit(fn, iters=20, warmup=5):
@@ -56,8 +170,13 @@ def main():
     ap.add_argument("--only", default="",
                     help="comma-separated substring filter on shape names")
     ap.add_argument("--passes", default="fwd,dgrad,wgrad")
+    ap.add_argument("--stats", action="store_true",
+                    help="1x1 forward + norm-statistics mode (use --batch "
+                         "1536 --out profiles/conv_stats_bench_b1536.md)")
     args = ap.parse_args()
     assert torch.cuda.is_available()
+    if args.stats:
+        return stats_mode(args)
     from dwt_amd.ops.mfma import conv2d_fwd, mfma_gemm
     dev = torch.device("cuda:0")
     lines = ["# MFMA implicit-GEMM conv/GEMM vs MIOpen/rocBLAS (bf16, NHWC)",

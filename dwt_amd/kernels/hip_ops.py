@@ -25,13 +25,19 @@ def _whiten_layout(x, c, g):
     g > 8 always routes NCHW (the generic LDS-tiled kernels)."""
     if x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last) \
             and not x.is_contiguous():
-        if c % 64 == 0 and (c <= 256 or c % 256 == 0) and g in (2, 4):
-            # g=8 NHWC instantiations spill registers (profiles/
-            # kernel_resources.md) — route them to the NCHW path
-            gw = min(c, 256) // g
-            if gw > 0 and 256 % gw == 0:
-                return "cl"
+        if whiten_cl_supported(c, g):
+            return "cl"
     return "nchw"
+
+
+def whiten_cl_supported(c, g):
+    """(C, g) the NHWC whitening kernels serve (see _whiten_layout)."""
+    if c % 64 == 0 and (c <= 256 or c % 256 == 0) and g in (2, 4):
+        # g=8 NHWC instantiations spill registers (profiles/
+        # kernel_resources.md) — route them to the NCHW path
+        gw = min(c, 256) // g
+        return gw > 0 and 256 % gw == 0
+    return False
 
 
 def _bn_cl_supported(c):
@@ -81,6 +87,19 @@ def _f32c(t):
     return t.detach().to(torch.float32).contiguous()
 
 
+def _usable_stats_acc(acc, x, layout, training, numel):
+    """``acc``: the pre-accumulated raw sums a producing conv handed over
+    (ops/mfma.py::conv1x1_stats), or None.  Returns them flat when this
+    forward can use them — NHWC training statistics of exactly this site's
+    size — else None: the site computes its own statistics."""
+    if acc is None or not training or layout != "cl" or x.dim() != 4:
+        return None
+    if acc.dtype != torch.float32 or acc.device != x.device \
+            or acc.numel() != numel or not acc.is_contiguous():
+        return None
+    return acc.detach().reshape(-1)
+
+
 class _HipWhitenMulti(torch.autograd.Function):
     """All per-branch statistics are STACKED ([parts*C] means, [parts*G, g, g]
     covariances/W) so the channels_last path runs ONE launch per pass across
@@ -95,6 +114,8 @@ class _HipWhitenMulti(torch.autograd.Function):
         # res (channels_last layout only; passed by _HipWhitenJoin, never
         # through apply): the apply pass writes relu(norm(x) + res)
         ext = _ext()
+        # taken out of cfg here, used or not: ctx.cfg keeps no tensor
+        stats_acc = cfg.pop("stats_acc", None)
         parts = cfg["parts"]
         g = x.shape[1] // cfg["num_groups"]
         eps, momentum = cfg["eps"], cfg["momentum"]
@@ -127,10 +148,19 @@ class _HipWhitenMulti(torch.autograd.Function):
 
         out = torch.empty_like(x)
         if use_batch:
-            acc = torch.zeros(ng_all * (g + g * g), device=dev, dtype=torch.float32)
+            acc = _usable_stats_acc(stats_acc, x, layout, training,
+                                    ng_all * (g + g * g))
+            pre = acc is not None
+            if not pre:
+                acc = torch.zeros(ng_all * (g + g * g), device=dev, dtype=torch.float32)
             mean = torch.empty(parts * c, device=dev, dtype=torch.float32)
             cov = torch.empty(ng_all, g, g, device=dev, dtype=torch.float32)
-            if stats_sync:
+            if pre:
+                # raw sums came from the producing conv's epilogue
+                if stats_sync and world > 1:
+                    _allreduce(acc)
+                ext.whiten_stats_final(acc, mean, cov, g, ng_all, ctx_count)
+            elif stats_sync:
                 # split pass: local raw sums -> all-reduce -> finalize over
                 # the GLOBAL batch (SyncBN-style cross-rank statistics)
                 if layout == "cl":
@@ -387,6 +417,7 @@ def whiten_multi(x, gamma, beta, running_means, running_vars, cfg):
                    f"dwt_amd: whiten_multi g={g} dtype={x.dtype} uses the "
                    "torch path (HIP kernels cover g <= 32, fp32/bf16)")
         from ..ops.functional import WhitenMulti
+        cfg.pop("stats_acc", None)  # the torch path takes its own statistics
         return WhitenMulti.apply(x, gamma, beta, running_means, running_vars, cfg)
     return _HipWhitenMulti.apply(x, gamma, beta, running_means, running_vars, cfg)
 
@@ -397,6 +428,7 @@ class _HipBatchNormMulti(torch.autograd.Function):
                 res=None):
         # res: as in _HipWhitenMulti.forward (passed by _HipBatchNormJoin)
         ext = _ext()
+        stats_acc = cfg.pop("stats_acc", None)  # as in _HipWhitenMulti
         parts = cfg["parts"]
         eps, momentum = cfg["eps"], cfg["momentum"]
         training, relu = cfg["training"], cfg["relu"]
@@ -426,11 +458,20 @@ class _HipBatchNormMulti(torch.autograd.Function):
 
         out = torch.empty_like(x)
         if use_batch:
-            acc = torch.zeros(parts * 2 * c, device=dev, dtype=torch.float32)
+            acc = _usable_stats_acc(stats_acc, x, layout, training,
+                                    parts * 2 * c)
+            pre = acc is not None
+            if not pre:
+                acc = torch.zeros(parts * 2 * c, device=dev, dtype=torch.float32)
             mean = torch.empty(parts * c, device=dev, dtype=torch.float32)
             istd = torch.empty(parts * c, device=dev, dtype=torch.float32)
             var_unb = torch.empty(parts * c, device=dev, dtype=torch.float32)
-            if stats_sync:
+            if pre:
+                if stats_sync and world > 1:
+                    _allreduce(acc)
+                ext.bn_stats_final(acc, mean, istd, var_unb, c, parts,
+                                   cnt_total, eps)
+            elif stats_sync:
                 if layout == "cl":
                     ext.bn_stats_partial_cl(x, acc, c, cnt, parts)
                 else:
@@ -597,6 +638,7 @@ class _HipBatchNormJoin(torch.autograd.Function):
 def batch_norm_multi(x, gamma, beta, running_means, running_vars, cfg):
     if x.dtype not in (torch.float32, torch.bfloat16):
         from ..ops.functional import BatchNormMulti
+        cfg.pop("stats_acc", None)
         return BatchNormMulti.apply(x, gamma, beta, running_means, running_vars, cfg)
     return _HipBatchNormMulti.apply(x, gamma, beta, running_means, running_vars, cfg)
 

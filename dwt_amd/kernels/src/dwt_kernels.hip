@@ -3382,6 +3382,9 @@ void mfma_conv2d_fwd(torch::Tensor x, torch::Tensor wgt, torch::Tensor bias,
                      int64_t Cin, int64_t P, int64_t Q, int64_t Cout,
                      int64_t KH, int64_t KW, int64_t stride, int64_t pad,
                      bool relu, bool has_bias);
+void conv1x1_stats(torch::Tensor x, torch::Tensor wgt, torch::Tensor out,
+                   torch::Tensor acc, int64_t kind, int64_t g, int64_t parts,
+                   int64_t max_workgroups);
 void mfma_conv2d_dgrad(torch::Tensor dy, torch::Tensor wd, torch::Tensor dx,
                        int64_t N, int64_t H, int64_t W, int64_t Cin,
                        int64_t P, int64_t Q, int64_t Cdy, int64_t KH,
@@ -3394,6 +3397,7 @@ void mfma_conv2d_wgrad(torch::Tensor dy, torch::Tensor x, torch::Tensor dw,
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mfma_gemm", &mfma_gemm);
   m.def("mfma_conv2d_fwd", &mfma_conv2d_fwd);
+  m.def("conv1x1_stats", &conv1x1_stats);
   m.def("mfma_conv2d_dgrad", &mfma_conv2d_dgrad);
   m.def("mfma_conv2d_wgrad", &mfma_conv2d_wgrad);
   m.def("whiten_stats", &whiten_stats);

@@ -401,6 +401,266 @@ __global__ __launch_bounds__(THREADS, PIPE ? 2 : 3) void conv_implicit_gemm_kern
 }
 
 // ===========================================================================
+// 1x1 stride-1 conv forward with the FOLLOWING norm site's raw statistics
+// taken in the epilogue: out[M,Cout] = x[M,Cin] @ w[Cout,Cin]^T (no bias, no
+// ReLU) plus, per domain branch (`parts` equal row ranges of M), the fp32
+// sums the stand-alone stats kernels would compute from `out` — so the norm
+// site skips its stats pass (a full re-read of `out` from HBM).
+//
+//   STATS_BN:      acc[part][2][Cout]      sums, sums of squares
+//   STATS_WHITEN4: acc[part*Cout/4+grp][4+16]  4 sums, then co-moments at
+//                  [4 + i*4 + j] for j <= i (what whiten_stats_final reads)
+//
+// Statistics use the bf16-ROUNDED value that is stored.  In the 16x16 C
+// fragment a lane holds one column (lane%16) and 4 rows per fragment, so the
+// per-column sums over a tile's 16 rows-per-lane are lane-local and a
+// whitening group of 4 channels is one lane quad (co-moments by quad-
+// broadcast DPP).  Per-lane partials go to a small LDS accumulator
+// (ds_add_f32) that lives ACROSS tiles: the kernel is persistent, each
+// workgroup walks a contiguous run of M-tiles of one N-tile and issues one
+// global atomic per statistic only when the run leaves a branch or ends
+// (guide G12: per-tile global atomics would be ~19 M adds on 1.5 K
+// addresses at l1.conv3).  The host guarantees (M/parts) % BM == 0, so a
+// tile never straddles two branches.
+//
+// The C tile is staged through the A/B LDS storage after the K loop's last
+// barrier and leaves as 16-byte row-contiguous stores (256 B per row per
+// wave) instead of the 2-byte stores of the generic epilogue above.
+// ===========================================================================
+
+enum StatsKind { STATS_BN = 0, STATS_WHITEN4 = 1 };
+
+constexpr int C_PITCH = BN + PAD_HALFS;  // C staging row pitch (halves)
+
+template <int CTRL>
+DEV_INLINE float quad_bcast(float v) {
+  union { int i; float f; } a, b;
+  a.f = v;
+  b.i = __builtin_amdgcn_mov_dpp(a.i, CTRL, 0xf, 0xf, true);
+  return b.f;
+}
+
+// Dense tile load for the kernel below: rows of `base` (row pitch K), zero
+// beyond `nrows` / K.  off[c] = row*K + kc of this thread's chunk c.
+DEV_INLINE void load_rows(const bf16* __restrict__ base, const int (&off)[4],
+                          int nrows, int K, int k0, StageRegs& rg) {
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const int idx = t + c * THREADS;
+    const int row = idx / (BK / 8);
+    const int kc = (idx % (BK / 8)) * 8;
+    if (row < nrows && k0 + kc < K)
+      rg.c[c] = *reinterpret_cast<const uint4*>(base + off[c] + k0);
+    else
+      rg.c[c] = make_uint4(0, 0, 0, 0);
+  }
+}
+
+template <bool PIPE, int KIND>
+__global__ __launch_bounds__(THREADS, PIPE ? 2 : 3) void conv1x1_stats_kernel(
+    const bf16* __restrict__ x, const bf16* __restrict__ wgt,
+    bf16* __restrict__ out, float* __restrict__ acc, ConvParams cp,
+    int mtiles, int ntiles, int tiles_per_part, int nlanes, int runs) {
+  constexpr int TILE = BM * LDS_PITCH;
+  constexpr int NBUF = PIPE ? 2 : 1;
+  constexpr int NV = KIND == STATS_BN ? 2 : 5;   // LDS stats per column
+  // [buf][a|b][TILE]; the C staging tile overlays it from offset 0
+  __shared__ __attribute__((aligned(16))) unsigned short lds[NBUF * 2 * TILE];
+  __shared__ float sacc[BN * NV];
+  static_assert(BM * C_PITCH <= 2 * TILE, "C staging must fit the A/B storage");
+
+  // XCD-aware bijective remap (as SWZ above): consecutive logical ids share
+  // an XCD, so the workgroups walking the same M-run for neighbouring
+  // N-tiles read their A tiles through one L2
+  int bid = blockIdx.x;
+  {
+    const int nwg = gridDim.x;
+    const int nx = 8;
+    const int qq = nwg / nx, rr = nwg % nx;
+    const int xcd = bid % nx, idx = bid / nx;
+    bid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + idx;
+  }
+  const int nlane = bid % nlanes;
+  const int run = bid / nlanes;
+  const int mt_begin = (int)((int64_t)run * mtiles / runs);
+  const int mt_end = (int)((int64_t)(run + 1) * mtiles / runs);
+
+  const int wave = threadIdx.x / 64;
+  const int lane = threadIdx.x % 64;
+  const int wm = (wave / 2) * 64;
+  const int wn = (wave % 2) * 64;
+  const int frag_row = lane % 16;
+  const int frag_koff = (lane / 16) * 8;
+  const int erow = (lane / 16) * 4;
+  const int ecol = lane % 16;
+  const int nk = (cp.K + BK - 1) / BK;
+
+  // A and B tiles stage with one chunk map: element offsets row*K + kc from
+  // a per-tile base pointer (32-bit, shared by both operands)
+  int off[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int idx = threadIdx.x + q * THREADS;
+    off[q] = (idx / (BK / 8)) * cp.K + (idx % (BK / 8)) * 8;
+  }
+
+  for (int k = threadIdx.x; k < BN * NV; k += THREADS) sacc[k] = 0.f;
+  __syncthreads();
+
+  for (int nt = nlane; nt < ntiles; nt += nlanes) {
+    const int n0 = nt * BN;
+    const bf16* wb = wgt + (int64_t)n0 * cp.K;
+    const int brows = cp.Cout - n0 < BN ? cp.Cout - n0 : BN;
+    for (int mt = mt_begin; mt < mt_end; ++mt) {
+      const int64_t m0 = (int64_t)mt * BM;
+
+      floatx4 c[4][4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) c[i][j] = (floatx4){0.f, 0.f, 0.f, 0.f};
+
+      StageRegs ra, rb;
+      const bf16* xa = x + m0 * cp.K;
+      const int arows = (int)(cp.M - m0 < BM ? cp.M - m0 : BM);
+      if (PIPE) {
+        load_rows(xa, off, arows, cp.K, 0, ra);
+        load_rows(wb, off, brows, cp.K, 0, rb);
+        write_tile(ra, lds);
+        write_tile(rb, lds + TILE);
+        __syncthreads();
+      }
+      for (int t = 0; t < nk; ++t) {
+        const int cur = PIPE ? (t & 1) : 0;
+        unsigned short* la = lds + (2 * cur) * TILE;
+        unsigned short* lb = la + TILE;
+        if (PIPE) {
+          if (t + 1 < nk) {
+            load_rows(xa, off, arows, cp.K, (t + 1) * BK, ra);
+            load_rows(wb, off, brows, cp.K, (t + 1) * BK, rb);
+          }
+        } else {
+          load_rows(xa, off, arows, cp.K, t * BK, ra);
+          load_rows(wb, off, brows, cp.K, t * BK, rb);
+          write_tile(ra, la);
+          write_tile(rb, lb);
+          __syncthreads();
+        }
+#pragma unroll
+        for (int ks = 0; ks < BK; ks += 32) {
+          short8 afrag[4], bfrag[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            afrag[i] = *reinterpret_cast<const short8*>(
+                la + (wm + i * 16 + frag_row) * LDS_PITCH + ks + frag_koff);
+            bfrag[i] = *reinterpret_cast<const short8*>(
+                lb + (wn + i * 16 + frag_row) * LDS_PITCH + ks + frag_koff);
+          }
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              c[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                  afrag[i], bfrag[j], c[i][j], 0, 0, 0);
+        }
+        if (PIPE) {
+          // the last k-step also ends on a barrier here: the C staging
+          // below overwrites both buffers
+          __syncthreads();
+          if (t + 1 < nk) {
+            const int nxt = cur ^ 1;
+            write_tile(ra, lds + (2 * nxt) * TILE);
+            write_tile(rb, lds + (2 * nxt + 1) * TILE);
+            __syncthreads();
+          }
+        } else {
+          __syncthreads();
+        }
+      }
+
+      // ---- epilogue: round, stage C in LDS, per-column statistics ----
+      // rows m >= M and columns n >= Cout hold exact zeros (their A / B
+      // rows were zero-filled), so they add nothing to the sums
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int col = wn + j * 16 + ecol;
+        float s = 0.f, p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const unsigned short u = f_to_bf16(c[i][j][r]);
+            const float v = bf16_to_f(u);
+            lds[(wm + i * 16 + erow + r) * C_PITCH + col] = u;
+            s += v;
+            if (KIND == STATS_BN) {
+              p0 += v * v;
+            } else {
+              p0 += v * quad_bcast<0x00>(v);
+              p1 += v * quad_bcast<0x55>(v);
+              p2 += v * quad_bcast<0xAA>(v);
+              p3 += v * quad_bcast<0xFF>(v);
+            }
+          }
+        }
+        if (KIND == STATS_BN) {
+          atomicAdd(&sacc[col], s);
+          atomicAdd(&sacc[BN + col], p0);
+        } else {
+          float* mine = sacc + col * NV;
+          atomicAdd(&mine[0], s);
+          atomicAdd(&mine[1], p0);
+          atomicAdd(&mine[2], p1);
+          atomicAdd(&mine[3], p2);
+          atomicAdd(&mine[4], p3);
+        }
+      }
+      __syncthreads();
+
+      // ---- C tile out: 16 B per lane, 16 lanes per 256-B row ----
+#pragma unroll
+      for (int q = 0; q < (BM * BN / 8) / THREADS; ++q) {
+        const int idx = threadIdx.x + q * THREADS;
+        const int row = idx / (BN / 8);
+        const int cc = (idx % (BN / 8)) * 8;
+        const int64_t m = m0 + row;
+        const int n = n0 + cc;
+        if (m < cp.M && n < cp.Cout)
+          *reinterpret_cast<uint4*>(out + m * cp.Cout + n) =
+              *reinterpret_cast<const uint4*>(lds + row * C_PITCH + cc);
+      }
+      __syncthreads();  // staging free again; this tile's sacc adds visible
+
+      // ---- flush when the run leaves this branch or ends ----
+      const int part = mt / tiles_per_part;
+      if (mt + 1 == mt_end || (mt + 1) / tiles_per_part != part) {
+        for (int k = threadIdx.x; k < BN * NV; k += THREADS) {
+          const float v = sacc[k];
+          sacc[k] = 0.f;
+          if (KIND == STATS_BN) {
+            const int which = k / BN;
+            const int n = n0 + k % BN;
+            if (n < cp.Cout)
+              atomicAdd(acc + ((int64_t)part * 2 + which) * cp.Cout + n, v);
+          } else {
+            const int n = n0 + k / NV;
+            const int e = k % NV;
+            const int i = n & 3;
+            if (n < cp.Cout && e <= i + 1) {
+              const int64_t grp = (int64_t)part * (cp.Cout / 4) + n / 4;
+              const int slot = e == 0 ? i : 4 + i * 4 + (e - 1);
+              atomicAdd(acc + grp * 20 + slot, v);
+            }
+          }
+        }
+        __syncthreads();
+      }
+    }
+  }
+}
+
+// ===========================================================================
 // wgrad v2: dw[co][(r,s,ci)] = sum_{k=npq} dy[k][co] * xpatch[k][(r,s,ci)]
 //
 // The K dimension is the (huge) output-position axis, so the kernel is
@@ -854,6 +1114,73 @@ void mfma_conv2d_fwd(Tensor x, Tensor wgt, Tensor bias, Tensor out,
   };
   if (gemm_fast) pick_rb(std::true_type{});
   else pick_rb(std::false_type{});
+}
+
+
+// 1x1 stride-1 conv forward + the next norm site's raw statistics.
+// x: raw NHWC storage of M = numel/Cin positions; wgt (Cout, Cin) storage;
+// out raw NHWC (M, Cout); acc fp32, ZEROED by the caller, laid out as the
+// finalize kernels read it (see conv1x1_stats_kernel).  kind: 0 = BN,
+// 1 = whitening (g must be 4).  max_workgroups: 0 = one resident wave of
+// workgroups for this device; tests pass 1 or 2 to force long runs.
+void conv1x1_stats(Tensor x, Tensor wgt, Tensor out, Tensor acc, int64_t kind,
+                   int64_t g, int64_t parts, int64_t max_workgroups) {
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 &&
+              wgt.scalar_type() == at::kBFloat16 &&
+              out.scalar_type() == at::kBFloat16 &&
+              acc.scalar_type() == at::kFloat, "conv1x1_stats: dtypes");
+  TORCH_CHECK(x.is_cuda() && wgt.is_cuda() && out.is_cuda() && acc.is_cuda());
+  TORCH_CHECK(wgt.dim() >= 2 && acc.is_contiguous());
+  const int64_t Cout = wgt.size(0);
+  const int64_t Cin = wgt.numel() / Cout;
+  TORCH_CHECK(Cin % 8 == 0 && Cout % 8 == 0, "conv1x1_stats: C % 8");
+  TORCH_CHECK(x.numel() % Cin == 0);
+  const int64_t M = x.numel() / Cin;
+  TORCH_CHECK(out.numel() == M * Cout);
+  TORCH_CHECK(parts >= 1 && M % parts == 0 && (M / parts) % dwtmm::BM == 0,
+              "conv1x1_stats: rows per branch must be a multiple of ",
+              dwtmm::BM);
+  TORCH_CHECK(kind == dwtmm::STATS_BN || (kind == dwtmm::STATS_WHITEN4 && g == 4),
+              "conv1x1_stats: BN or whitening with g = 4 only");
+  const int64_t acc_n = kind == dwtmm::STATS_BN ? parts * 2 * Cout
+                                                : parts * (Cout / 4) * 20;
+  TORCH_CHECK(acc.numel() == acc_n, "conv1x1_stats: acc size");
+  TORCH_CHECK(M / dwtmm::BM < (int64_t)1 << 31);
+
+  dwtmm::ConvParams cp{};
+  cp.M = M; cp.K = (int)Cin; cp.Cout = (int)Cout;
+  const int mtiles = (int)(M / dwtmm::BM);
+  const int ntiles = (int)((Cout + dwtmm::BN - 1) / dwtmm::BN);
+  const bool pipe = cp.K >= 4 * dwtmm::BK;
+  int64_t maxwg = max_workgroups;
+  if (maxwg <= 0) {
+    // queried once: the CU count of whichever device is current on the
+    // first call serves every device (the supported boxes are homogeneous)
+    static const int cus =
+        at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+    maxwg = (int64_t)cus * (pipe ? 2 : 3);
+  }
+  const int nlanes = (int)std::min<int64_t>(maxwg, ntiles);
+  const int runs = (int)std::max<int64_t>(
+      1, std::min<int64_t>(maxwg / nlanes, mtiles));
+  auto launch = [&](auto pipec, auto kindc) {
+    hipLaunchKernelGGL(
+        (dwtmm::conv1x1_stats_kernel<decltype(pipec)::value,
+                                     decltype(kindc)::value>),
+        dim3(nlanes * runs), dim3(dwtmm::THREADS), 0, dwtmm_stream(),
+        (const c10::BFloat16*)x.data_ptr(), (const c10::BFloat16*)wgt.data_ptr(),
+        (c10::BFloat16*)out.data_ptr(), acc.data_ptr<float>(), cp, mtiles,
+        ntiles, (int)(M / parts / dwtmm::BM), nlanes, runs);
+  };
+  using KBN = std::integral_constant<int, dwtmm::STATS_BN>;
+  using KWH = std::integral_constant<int, dwtmm::STATS_WHITEN4>;
+  if (kind == dwtmm::STATS_BN) {
+    if (pipe) launch(std::true_type{}, KBN{});
+    else launch(std::false_type{}, KBN{});
+  } else {
+    if (pipe) launch(std::true_type{}, KWH{});
+    else launch(std::false_type{}, KWH{});
+  }
 }
 
 

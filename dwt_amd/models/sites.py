@@ -35,6 +35,7 @@ def norm_site(
     relu: bool,
     eval_branch: int = 1,
     residual: Optional[torch.Tensor] = None,
+    stats_acc: Optional[torch.Tensor] = None,
 ):
     """Apply a multi-domain norm site.
 
@@ -46,9 +47,16 @@ def norm_site(
     With ``residual`` the site is a bottleneck exit: the result is the pair
     ``(y_a, y_b)`` of ``Fdwt.norm_join``, both ``relu(norm(x) + residual)``
     (``relu`` must be True — it follows the add), one per consumer.
+
+    ``stats_acc``: the raw batch statistics of ``x`` when the conv that
+    produced it accumulated them already (``ops.mfma.conv1x1_stats``).  The
+    HIP NHWC training forward then skips its stats pass; eval and every other
+    path compute what they need themselves.
     """
     if residual is not None:
         assert relu, "a residual join applies its ReLU after the add"
+    if not training:
+        stats_acc = None
     first = branches[0]
     if training:
         use = list(branches)
@@ -62,7 +70,8 @@ def norm_site(
         w0 = whs[0]
         kw = dict(parts=parts, num_groups=w0.num_groups, eps=w0.eps,
                   momentum=w0.momentum, training=training, mode=w0.mode,
-                  track_running_stats=w0.track_running_stats)
+                  track_running_stats=w0.track_running_stats,
+                  stats_acc=stats_acc)
         rms = [w.running_mean for w in whs]
         rvs = [w.running_variance for w in whs]
         if residual is not None:
@@ -86,7 +95,8 @@ def norm_site(
         rvs = [b.running_var for b in use] if first.track_running_stats else None
         kw = dict(parts=parts, eps=first.eps, momentum=momentum,
                   training=training,
-                  track_running_stats=first.track_running_stats)
+                  track_running_stats=first.track_running_stats,
+                  stats_acc=stats_acc)
         if residual is not None:
             return Fdwt.norm_join("bn", x, residual, gamma, beta, rms, rvs, **kw)
         return Fdwt.batch_norm_multi(x, gamma, beta, rms, rvs, relu=relu, **kw)

@@ -351,7 +351,12 @@ def whiten_multi(
     relu: bool = False,
     ns_iters: int = 7,
     track_running_stats: bool = True,
+    stats_acc: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
+    """``stats_acc``: raw statistics of ``x`` that the conv producing it
+    already accumulated (ops/mfma.py::conv1x1_stats).  Only the HIP NHWC
+    training forward uses it, in place of its stats pass; every other path
+    ignores it and computes its own."""
     cfg = _whiten_cfg(parts=parts, num_groups=num_groups, eps=eps,
                       momentum=momentum, training=training, mode=mode,
                       relu=relu, ns_iters=ns_iters,
@@ -359,6 +364,8 @@ def whiten_multi(
     if x.is_cuda:
         from ..kernels import dispatch
         if dispatch.available():
+            if stats_acc is not None:
+                cfg["stats_acc"] = stats_acc
             return dispatch.whiten_multi(x, gamma, beta, running_means, running_vars, cfg)
         dispatch.require_or_warn("whiten_multi")
     return WhitenMulti.apply(x, gamma, beta, running_means, running_vars, cfg)
@@ -519,12 +526,16 @@ def batch_norm_multi(
     training: bool = True,
     relu: bool = False,
     track_running_stats: bool = True,
+    stats_acc: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
+    """``stats_acc``: as in :func:`whiten_multi`."""
     cfg = _bn_cfg(parts=parts, eps=eps, momentum=momentum, training=training,
                   relu=relu, track_running_stats=track_running_stats)
     if x.is_cuda:
         from ..kernels import dispatch
         if dispatch.available():
+            if stats_acc is not None:
+                cfg["stats_acc"] = stats_acc
             return dispatch.batch_norm_multi(x, gamma, beta, running_means, running_vars, cfg)
         dispatch.require_or_warn("batch_norm_multi")
     return BatchNormMulti.apply(x, gamma, beta, running_means, running_vars, cfg)
@@ -686,18 +697,23 @@ def norm_join(
     """
     assert kind in ("whiten", "bn"), kind
     kw = dict(kw, relu=False)
+    # pre-accumulated statistics of x (see whiten_multi); both paths take it
+    stats_acc = kw.pop("stats_acc", None)
     if x.is_cuda and fused_join_enabled():
         from ..kernels import dispatch
         if dispatch.available():
             from ..kernels import hip_ops
             cfg = _whiten_cfg(**kw) if kind == "whiten" else _bn_cfg(**kw)
             if hip_ops.join_supported(kind, x, identity, cfg):
+                if stats_acc is not None:
+                    cfg["stats_acc"] = stats_acc
                 fn = hip_ops.whiten_join if kind == "whiten" \
                     else hip_ops.batch_norm_join
                 return fn(x, identity, gamma, beta, running_means,
                           running_vars, cfg)
     multi = whiten_multi if kind == "whiten" else batch_norm_multi
-    y = add_relu(multi(x, gamma, beta, running_means, running_vars, **kw),
+    y = add_relu(multi(x, gamma, beta, running_means, running_vars,
+                       stats_acc=stats_acc, **kw),
                  identity)
     return y, y
 

@@ -120,6 +120,156 @@ def conv2d_fwd(x: torch.Tensor, weight: torch.Tensor,
     return out
 
 
+# ----------------------------------------------------------------------------
+# 1x1 conv forward with the following norm site's statistics in its epilogue
+# ----------------------------------------------------------------------------
+
+STATS_TILE_M = 128     # the kernel's M tile: rows per branch must divide by it
+_STATS_KINDS = {"bn": 0, "whiten": 1}
+
+
+def fused_conv_stats_enabled() -> bool:
+    """``DWT_AMD_FUSED_CONV_STATS=0`` sends every 1x1 conv back to the library
+    forward + stand-alone stats kernel.  Read on every call."""
+    import os
+    return os.environ.get("DWT_AMD_FUSED_CONV_STATS", "1") != "0"
+
+
+def stats_acc_numel(kind: str, c: int, parts: int, g: int = 4) -> int:
+    """Size of the raw-sums accumulator the finalize kernels read: BN
+    ``[parts][2][C]``; whitening ``[parts*C/g][g + g*g]``."""
+    if kind == "bn":
+        return parts * 2 * c
+    return parts * (c // g) * (g + g * g)
+
+
+def conv_stats_shape_ok(m: int, cin: int, cout: int) -> bool:
+    """Shapes where the fused conv beats library forward + stats kernel by
+    more than 5% at N = 1536 (profiles/conv_stats_bench_b1536.md).
+
+    Every shape with K = Cin >= 128 and Cout >= 128 wins by 1.33-1.66x, at
+    each M measured (75 K to 4.8 M rows), so M does not enter.  The three
+    layer-1 shapes (Cin or Cout = 64) lose, 0.48-0.67x: one k-step and a
+    64-wide output leave nothing for the epilogue to hide under."""
+    del m
+    return cin >= _ROUTE_MIN_C and cout >= _ROUTE_MIN_C
+
+
+_ROUTE_MIN_C = 128
+
+
+def conv_stats_route(conv, x: torch.Tensor, branches, training: bool):
+    """``(kind, g, parts)`` when ``conv`` followed by the norm site
+    ``branches`` can run as :func:`conv1x1_stats` on ``x``, else ``None``."""
+    if not training or not fused_conv_stats_enabled():
+        return None
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
+            and x.is_contiguous(memory_format=torch.channels_last)):
+        return None
+    if type(conv) is not nn.Conv2d or conv.bias is not None \
+            or conv.kernel_size != (1, 1) or conv.stride != (1, 1) \
+            or conv.padding != (0, 0) or conv.dilation != (1, 1) \
+            or conv.groups != 1 or conv.weight.dtype != torch.bfloat16:
+        return None
+    from ..kernels import dispatch
+    if not dispatch.available():
+        return None
+    from ..kernels import hip_ops
+    from .whitening import WhiteningScaleShift, WTransform2d
+    from .batch_norm import _DomainBatchNorm
+    n, cin, h, w = x.shape
+    cout = conv.out_channels
+    parts = len(branches)
+    first = branches[0]
+    if isinstance(first, (WhiteningScaleShift, WTransform2d)):
+        wh = first.wh if isinstance(first, WhiteningScaleShift) else first
+        g = cout // wh.num_groups
+        if g != 4 or not hip_ops.whiten_cl_supported(cout, g):
+            return None
+        kind = "whiten"
+    elif isinstance(first, _DomainBatchNorm):
+        if not hip_ops._bn_cl_supported(cout):
+            return None
+        kind, g = "bn", 0
+    else:
+        return None
+    if h * w == 1 or cout == 1:
+        return None  # channels_last is ambiguous there; keep the old path
+    if cin % 8 or cout % 8 or n % parts \
+            or (n // parts * h * w) % STATS_TILE_M:
+        return None
+    if not conv_stats_shape_ok(n * h * w, cin, cout):
+        return None
+    return kind, g, parts
+
+
+class _Conv1x1StatsFn(torch.autograd.Function):
+    """Forward: the persistent MFMA GEMM with the stats epilogue.  Backward:
+    the library's dgrad / wgrad, the kernels the step runs without fusion."""
+
+    calls = 0   # forward launches (tests assert the fused path really ran)
+
+    @staticmethod
+    def forward(ctx, x, weight, kind, g, parts, max_workgroups):
+        n, cin, h, w = x.shape
+        cout = weight.shape[0]
+        out = torch.empty(n, cout, h, w, device=x.device, dtype=torch.bfloat16,
+                          memory_format=torch.channels_last)
+        acc = torch.zeros(stats_acc_numel(kind, cout, parts), device=x.device,
+                          dtype=torch.float32)
+        wgt = weight.detach().reshape(cout, cin).contiguous()
+        _ext().conv1x1_stats(x, wgt, out, acc, _STATS_KINDS[kind], g, parts,
+                             max_workgroups)
+        _Conv1x1StatsFn.calls += 1
+        ctx.save_for_backward(x, weight)
+        ctx.mark_non_differentiable(acc)
+        return out, acc
+
+    @staticmethod
+    def backward(ctx, dout, _dacc):
+        x, weight = ctx.saved_tensors
+        dx, dw, _ = torch.ops.aten.convolution_backward(
+            dout, x, weight, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
+            [ctx.needs_input_grad[0], True, False])
+        return dx, dw, None, None, None, None
+
+
+def conv1x1_stats(x: torch.Tensor, weight: torch.Tensor, kind: str,
+                  g: int = 4, parts: int = 3, max_workgroups: int = 0):
+    """1x1 stride-1 bias-free conv of channels_last bf16 ``x`` that also
+    returns the raw statistics accumulator of the norm site that follows
+    (``kind`` "bn" or "whiten" with g = 4; ``parts`` equal batch ranges, each
+    a multiple of 128 positions).  Hand ``acc`` to ``norm_site(stats_acc=)``.
+
+    Where the kernel does not apply (another device, dtype, layout or group
+    size, rows per branch no multiple of 128) this is ``(F.conv2d(x, weight),
+    None)``: the norm site then takes its own statistics.
+    """
+    assert kind in _STATS_KINDS, kind
+    if not _conv1x1_stats_applies(x, weight, kind, g, parts):
+        return F.conv2d(x, weight), None
+    return _Conv1x1StatsFn.apply(x, weight, kind, g, parts, max_workgroups)
+
+
+def _conv1x1_stats_applies(x, weight, kind, g, parts) -> bool:
+    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.bfloat16
+            and weight.dtype == torch.bfloat16
+            and x.is_contiguous(memory_format=torch.channels_last)):
+        return False
+    if weight.dim() != 4 or weight.shape[2:] != (1, 1) \
+            or weight.shape[1] != x.shape[1]:
+        return False
+    n, cin, h, w = x.shape
+    cout = weight.shape[0]
+    if kind == "whiten" and g != 4:
+        return False
+    if cin % 8 or cout % 8 or parts < 1 or n % parts \
+            or (n // parts * h * w) % STATS_TILE_M:
+        return False
+    from ..kernels import dispatch
+    return dispatch.available()
+
+
 def conv2d_dgrad(dy: torch.Tensor, weight: torch.Tensor, in_shape,
                  stride: int = 1, padding: int = 0) -> torch.Tensor:
     """dx for an NHWC conv: implicit GEMM over dy with the weight permuted to

@@ -41,6 +41,25 @@ def grouped_cov(xn: torch.Tensor, num_groups: int) -> torch.Tensor:
     return torch.bmm(t, t.transpose(1, 2)) / t.shape[-1]
 
 
+def stats_acc_reference(out: torch.Tensor, kind: str, parts: int, g: int = 4,
+                        dtype=torch.float64) -> torch.Tensor:
+    """Raw-sums accumulator of a norm site, as the HIP stats kernels and the
+    conv epilogue (kernels/src/mfma_conv.hip::conv1x1_stats_kernel) lay it
+    out, from an (N, C, H, W) tensor split into ``parts`` batch ranges.
+
+    ``kind`` "bn": per branch ``[2][C]``, sums then sums of squares.
+    ``kind`` "whiten": per (branch, group) ``[g + g*g]``, the g sums followed
+    by the co-moment matrix with only ``j <= i`` filled."""
+    c = out.shape[1]
+    v = out.detach().to(dtype).permute(0, 2, 3, 1).reshape(parts, -1, c)
+    if kind == "bn":
+        return torch.stack([v.sum(1), (v * v).sum(1)], dim=1).reshape(-1)
+    t = v.reshape(parts, v.shape[1], c // g, g)
+    sums = t.sum(1)                                       # (parts, G, g)
+    pm = torch.tril(torch.einsum("pmgi,pmgj->pgij", t, t))
+    return torch.cat([sums, pm.reshape(parts, c // g, g * g)], dim=2).reshape(-1)
+
+
 def shrink_cov(cov: torch.Tensor, eps: float) -> torch.Tensor:
     """Shrinkage toward identity: (1-eps) * cov + eps * I (whitening.py:48)."""
     g = cov.shape[-1]
