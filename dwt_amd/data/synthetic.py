@@ -55,16 +55,34 @@ class SyntheticOfficeHome(data.Dataset):
 
     Generated on the fly (deterministic per index) so a benchmark-size
     dataset costs no memory.
+
+    ``uint8=True`` yields what a decoder + Resize would: a uint8
+    ``[img_size, img_size, 3]`` HWC frame for the device-side input pipeline
+    (``data/device_pipeline.py``), which crops, augments and normalizes it on
+    the device — so this mode takes no ``transform_aug``.
     """
 
     def __init__(self, n=2048, num_classes=65, img_size=224, transform=None,
-                 transform_aug=None, seed=0):
+                 transform_aug=None, seed=0, uint8=False):
+        if uint8 and transform_aug is not None:
+            raise ValueError("uint8 frames get their augmented view on the "
+                             "device; transform_aug does not apply")
         self.n = n
         self.num_classes = num_classes
         self.img_size = img_size
         self.transform = transform
         self.transform_aug = transform_aug
         self.seed = seed
+        self.uint8 = uint8
+
+    def _sample_uint8(self, index):
+        g = torch.Generator().manual_seed(self.seed * 1000003 + index)
+        label = int(torch.randint(0, self.num_classes, (1,), generator=g))
+        img = torch.randint(0, 256, (self.img_size, self.img_size, 3),
+                            generator=g, dtype=torch.uint8)
+        # class-dependent brightness of the red channel, like _sample
+        img[..., 0] = img[..., 0] // 2 + (128 * label) // self.num_classes
+        return img, label
 
     def _sample(self, index):
         g = torch.Generator().manual_seed(self.seed * 1000003 + index)
@@ -74,6 +92,11 @@ class SyntheticOfficeHome(data.Dataset):
         return img, label
 
     def __getitem__(self, index):
+        if self.uint8:
+            img, label = self._sample_uint8(index)
+            if self.transform is not None and callable(self.transform):
+                img = self.transform(img)
+            return img, torch.as_tensor(label, dtype=torch.long)
         img, label = self._sample(index)
         aug = None
         if self.transform_aug is not None:

@@ -3,7 +3,8 @@
 Covers exactly what the reference pipelines use
 (usps_mnist.py:355-386, resnet50_dwt_mec_officehome.py:527-543):
 Compose / Resize / RandomCrop / RandomHorizontalFlip / ToTensor /
-Normalize / Lambda.  Input images are PIL Images or HWC numpy arrays.
+Normalize / Lambda, plus ToUint8HWC for the device-side input pipeline.
+Input images are PIL Images or HWC numpy arrays.
 """
 from __future__ import annotations
 
@@ -99,6 +100,25 @@ class ToTensor:
         if t.dtype == torch.uint8:
             return t.float().div_(255.0)
         return t.float()
+
+
+class ToUint8HWC:
+    """PIL/HWC-numpy -> uint8 [H, W, 3] tensor: the frame format of the
+    device-side input pipeline (``data/device_pipeline.py``).  Float arrays
+    are taken as [0, 1]; single-channel input is repeated to three."""
+
+    def __call__(self, img):
+        if Image is not None and isinstance(img, Image.Image):
+            arr = np.asarray(img.convert("RGB"))
+        else:
+            arr = Resize._to_uint8(np.asarray(img))
+            if arr.ndim == 2:
+                arr = arr[:, :, None]
+            if arr.shape[2] == 1:
+                arr = np.repeat(arr, 3, axis=2)
+        if arr.ndim != 3 or arr.shape[2] != 3:
+            raise ValueError(f"expected an [H, W, 3] image, got {arr.shape}")
+        return torch.from_numpy(np.array(arr))   # a writable copy
 
 
 class Normalize:

@@ -6,6 +6,11 @@ source third + lambda * MEC on the two target views, SGD step, periodic eval;
 after training, a target-stats re-estimation pass (`eval_pass_collect_stats`)
 then the final test.  Adds (new vs reference): checkpoint save/resume,
 JSONL metrics, data-parallel gradient sync hook.
+
+Every loop takes ``batcher=None``.  With a ``data.DeviceBatcher`` the loaders
+yield uint8 HWC frames and the batcher builds each model batch on the device
+(crop, flip, affine, normalize, cast, NHWC — one kernel); with ``None`` the
+loaders' float tensors are used as they always were.
 """
 from __future__ import annotations
 
@@ -18,7 +23,8 @@ from ..ops import functional as Fdwt
 from .meters import JsonlLogger, ThroughputMeter
 
 
-def eval_pass_collect_stats(args, model, device, target_test_loader, passes=10):
+def eval_pass_collect_stats(args, model, device, target_test_loader, passes=10,
+                            batcher=None):
     """Re-estimate EMA stats with target data in all three streams
     (resnet50_dwt_mec_officehome.py:380-389)."""
     model.train(mode=True)
@@ -27,7 +33,10 @@ def eval_pass_collect_stats(args, model, device, target_test_loader, passes=10):
         for i in range(passes):
             print("Pass {} ...".format(i))
             for data, _ in target_test_loader:
-                data = torch.cat((data, data, data), dim=0).to(device).to(dtype)
+                if batcher is not None:
+                    data = batcher.eval_batch(data, streams=3)
+                else:
+                    data = torch.cat((data, data, data), dim=0).to(device).to(dtype)
                 model(data)
 
 
@@ -36,7 +45,7 @@ def train_infinite_collect_stats(args, model, device, source_train_loader,
                                  target_test_loader, logger: JsonlLogger = None,
                                  grad_sync=None, start_iter=0,
                                  checkpoint_path=None, checkpoint_every=0,
-                                 stats_passes=10):
+                                 stats_passes=10, batcher=None):
     source_iter = iter(source_train_loader)
     target_iter = iter(target_train_loader)
     exp_lr_scheduler = lr_scheduler.MultiStepLR(optimizer, milestones=[6000], gamma=0.1)
@@ -52,7 +61,7 @@ def train_infinite_collect_stats(args, model, device, source_train_loader,
                            optimizer, exp_lr_scheduler, lambda_mec_loss,
                            target_test_loader, logger, grad_sync, start_iter,
                            checkpoint_path, checkpoint_every, stats_passes,
-                           dtype, tp, progress)
+                           dtype, tp, progress, batcher)
     except Exception:
         # failure handling: persist an emergency checkpoint so a
         # torchrun restart can --resume instead of losing the run
@@ -71,7 +80,7 @@ def _train_loop(args, model, device, source_iter, target_iter,
                 source_train_loader, target_train_loader, optimizer,
                 exp_lr_scheduler, lambda_mec_loss, target_test_loader, logger,
                 grad_sync, start_iter, checkpoint_path, checkpoint_every,
-                stats_passes, dtype, tp, progress=None):
+                stats_passes, dtype, tp, progress=None, batcher=None):
     for i in range(start_iter, args.num_iters):
         if progress is not None:
             progress["iter"] = i
@@ -91,7 +100,11 @@ def _train_loop(args, model, device, source_iter, target_iter,
             tb = next(target_iter)
 
         gpu_aug = getattr(args, "gpu_augment", False)
-        if gpu_aug:
+        if batcher is not None:
+            # loaders yield uint8 HWC frames; the batcher copies them to the
+            # device (non_blocking) and writes all three streams in one launch
+            data = batcher.train_batch(source_data, tb[0])
+        elif gpu_aug:
             # loader yields (data, label); the duplicate MEC view is built
             # on-device (batched flip + affine — data/augment.py)
             from ..data import augment
@@ -128,7 +141,8 @@ def _train_loop(args, model, device, source_iter, target_iter,
                            mec_loss=mec_loss.item(), imgs_per_sec=ips)
 
         if (i + 1) % args.check_acc_step == 0:
-            test(args, model, device, target_test_loader, logger=logger)
+            test(args, model, device, target_test_loader, logger=logger,
+                 batcher=batcher)
 
         if checkpoint_path and checkpoint_every and (i + 1) % checkpoint_every == 0:
             ckpt.save_training_state(checkpoint_path, model, optimizer,
@@ -137,19 +151,24 @@ def _train_loop(args, model, device, source_iter, target_iter,
     print("Training is complete...")
     print("Running a bunch of forward passes to estimate the population statistics of target...")
     eval_pass_collect_stats(args, model, device, target_test_loader,
-                            passes=stats_passes)
+                            passes=stats_passes, batcher=batcher)
     print("Finally computing the precision on the test set...")
-    return test(args, model, device, target_test_loader, logger=logger)
+    return test(args, model, device, target_test_loader, logger=logger,
+                batcher=batcher)
 
 
-def test(args, model, device, target_test_loader, logger: JsonlLogger = None):
+def test(args, model, device, target_test_loader, logger: JsonlLogger = None,
+         batcher=None):
     model.eval()
     test_loss = 0.0
     correct = 0
     dtype = next(model.parameters()).dtype
     with torch.no_grad():
         for data, target in target_test_loader:
-            data = data.to(device).to(dtype)
+            if batcher is not None:
+                data = batcher.eval_batch(data, streams=1)
+            else:
+                data = data.to(device).to(dtype)
             target = target.to(device)
             output = model(data).float()
             test_loss += F.nll_loss(F.log_softmax(output, dim=1), target,

@@ -3394,7 +3394,14 @@ void mfma_conv2d_wgrad(torch::Tensor dy, torch::Tensor x, torch::Tensor dw,
                        int64_t Cin, int64_t P, int64_t Q, int64_t Cout,
                        int64_t KH, int64_t KW, int64_t stride, int64_t pad);
 
+// defined in input_pipeline.hip
+void assemble_views(torch::Tensor images, torch::Tensor src_index,
+                    torch::Tensor top, torch::Tensor left, torch::Tensor flags,
+                    torch::Tensor inv_affine, torch::Tensor out,
+                    std::vector<double> mean, std::vector<double> std_);
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("assemble_views", &assemble_views);
   m.def("mfma_gemm", &mfma_gemm);
   m.def("mfma_conv2d_fwd", &mfma_conv2d_fwd);
   m.def("conv1x1_stats", &conv1x1_stats);

@@ -15,8 +15,9 @@ from torch.utils.data import DataLoader, distributed as dist_data
 
 from dwt_amd.data import (Compose, ImageFolder, Lambda, Normalize, RandomCrop,
                           RandomHorizontalFlip, Resize, SyntheticOfficeHome,
-                          ToTensor)
+                          ToTensor, ToUint8HWC)
 from dwt_amd.data.augment import gaussian_blur, random_affine_augmentation
+from dwt_amd.data.device_pipeline import DeviceBatcher
 from dwt_amd.engine.meters import JsonlLogger
 from dwt_amd.engine.officehome import train_infinite_collect_stats
 from dwt_amd.models import resnet50, Bottleneck, ResNetDWT
@@ -66,16 +67,48 @@ def build_args(argv=None):
                              "cross-rank synced batch stats")
     parser.add_argument('--stats_passes', type=int, default=10,
                         help='target-stats re-estimation passes before final test')
-    parser.add_argument('--gpu_augment', action='store_true',
-                        help='build the duplicate MEC target view on-device '
-                             '(batched flip+affine) instead of in the CPU '
-                             'loader workers — keeps 8-GPU runs unstarved')
+    on_device = parser.add_mutually_exclusive_group()
+    on_device.add_argument('--gpu_augment', action='store_true',
+                           help='build the duplicate MEC target view on-device '
+                                '(batched flip+affine) instead of in the CPU '
+                                'loader workers — keeps 8-GPU runs unstarved')
+    on_device.add_argument('--device_pipeline', action='store_true',
+                           help='loaders yield resized uint8 HWC frames; one '
+                                'HIP kernel writes the (source, target, '
+                                'target_aug) batch — crop, flip, affine, '
+                                'normalize — in the model dtype and NHWC, and '
+                                'the model runs channels_last')
     return parser.parse_args(argv)
+
+
+MEAN, STD = [0.485, 0.456, 0.406], [0.229, 0.224, 0.225]
+
+
+def build_datasets_uint8(args):
+    """--device_pipeline: frames stay uint8 HWC at img_resize; the crop and
+    every augmentation happen on the device (no transform_aug)."""
+    if args.synthetic:
+        src = SyntheticOfficeHome(args.synthetic_size, args.num_classes,
+                                  args.img_resize, seed=1, uint8=True)
+        tgt = SyntheticOfficeHome(args.synthetic_size, args.num_classes,
+                                  args.img_resize, seed=2, uint8=True)
+        tgt_test = SyntheticOfficeHome(max(args.synthetic_size // 4, 64),
+                                       args.num_classes, args.img_resize,
+                                       seed=2, uint8=True)
+    else:
+        frames = Compose([Resize((args.img_resize, args.img_resize)),
+                          ToUint8HWC()])
+        src = ImageFolder(root=args.s_dset_path, transform=frames)
+        tgt = ImageFolder(root=args.t_dset_path, transform=frames)
+        tgt_test = ImageFolder(root=args.t_dset_path, transform=frames)
+    return src, tgt, tgt_test
 
 
 def build_loaders(args, rank, world):
     aug_in_loader = not getattr(args, 'gpu_augment', False)
-    if args.synthetic:
+    if getattr(args, 'device_pipeline', False):
+        src, tgt, tgt_test = build_datasets_uint8(args)
+    elif args.synthetic:
         src = SyntheticOfficeHome(args.synthetic_size, args.num_classes,
                                   args.img_crop_size, seed=1)
         tgt = SyntheticOfficeHome(args.synthetic_size, args.num_classes,
@@ -145,6 +178,14 @@ def main(argv=None):
         model = resnet50(args.resnet_path, device, num_classes=args.num_classes,
                          group_size=args.group_size, whiten_mode=args.whiten_mode)
     model = model.to(device).to(dtype)
+    batcher = None
+    if args.device_pipeline:
+        if device.type == 'cuda':
+            # the batcher writes NHWC, so the model takes the channels_last
+            # kernels (fused join, conv-epilogue statistics, NHWC norms)
+            model = model.to(memory_format=torch.channels_last)
+        batcher = DeviceBatcher(args.img_crop_size, MEAN, STD, dtype, device,
+                                seed=args.seed * 1000 + rank)
 
     final_layer_params, rest = [], []
     for name, param in model.named_parameters():
@@ -172,7 +213,8 @@ def main(argv=None):
         target_test_loader=test_loader, logger=logger,
         grad_sync=ddp.sync if ddp.enabled else None, start_iter=start_iter,
         checkpoint_path=args.checkpoint_path or None,
-        checkpoint_every=args.checkpoint_every, stats_passes=args.stats_passes)
+        checkpoint_every=args.checkpoint_every, stats_passes=args.stats_passes,
+        batcher=batcher)
     logger.close()
 
 
