@@ -59,6 +59,29 @@ def _bn_layout(x, c):
     return "nchw"
 
 
+def _flat_affine(gamma, beta, c, like):
+    """(has_affine, gamma, beta) with the affine flattened to (C,) for the
+    kernels; empty placeholders without one."""
+    if gamma is None:
+        return False, torch.empty(0, device=like.device, dtype=like.dtype), \
+            torch.empty(0, device=like.device, dtype=like.dtype)
+    return True, gamma.detach().reshape(c).contiguous(), \
+        beta.detach().reshape(c).contiguous()
+
+
+def _ema_update(ext, rm, new_mean, rv, new_var, momentum):
+    """Running-statistics EMA: the fused kernel on fp32 contiguous buffers,
+    mul_/add_ otherwise."""
+    if rm.dtype == torch.float32 and rm.is_contiguous() \
+            and rv.dtype == torch.float32 and rv.is_contiguous():
+        ext.ema_update(rm, new_mean, rv, new_var, momentum)
+    else:
+        rm.mul_(1.0 - momentum).add_(
+            new_mean.reshape(rm.shape).to(rm.dtype), alpha=momentum)
+        rv.mul_(1.0 - momentum).add_(
+            new_var.reshape(rv.shape).to(rv.dtype), alpha=momentum)
+
+
 def _warn_once(key, msg):
     if key not in _warned:
         _warned.add(key)
@@ -136,9 +159,7 @@ class _HipWhitenMulti(torch.autograd.Function):
         dev = x.device
         m_count = b * h * w
 
-        has_affine = gamma is not None
-        gflat = gamma.detach().reshape(c).contiguous() if has_affine else torch.empty(0, device=dev, dtype=x.dtype)
-        bflat = beta.detach().reshape(c).contiguous() if has_affine else torch.empty(0, device=dev, dtype=x.dtype)
+        has_affine, gflat, bflat = _flat_affine(gamma, beta, c, x)
 
         stats_sync = cfg.get("stats_sync", False) and use_batch
         world = 1
@@ -216,17 +237,9 @@ class _HipWhitenMulti(torch.autograd.Function):
         if training and track and running_means is not None:
             with torch.no_grad():
                 for p in range(parts):
-                    rm, rv = running_means[p], running_vars[p]
-                    mslice = mean[p * c:(p + 1) * c]
-                    cslice = cov[p * n_groups:(p + 1) * n_groups]
-                    if rm.dtype == torch.float32 and rm.is_contiguous() \
-                            and rv.dtype == torch.float32 and rv.is_contiguous():
-                        ext.ema_update(rm, mslice, rv, cslice, momentum)
-                    else:
-                        rm.mul_(1.0 - momentum).add_(
-                            mslice.reshape(rm.shape).to(rm.dtype), alpha=momentum)
-                        rv.mul_(1.0 - momentum).add_(
-                            cslice.reshape(rv.shape).to(rv.dtype), alpha=momentum)
+                    _ema_update(ext, running_means[p], mean[p * c:(p + 1) * c],
+                                running_vars[p],
+                                cov[p * n_groups:(p + 1) * n_groups], momentum)
 
         ctx.cfg = cfg
         ctx.g = g
@@ -446,9 +459,7 @@ class _HipBatchNormMulti(torch.autograd.Function):
         dev = x.device
         cnt = (x.numel() // parts) // c
 
-        has_affine = gamma is not None
-        gflat = gamma.detach().reshape(c).contiguous() if has_affine else torch.empty(0, device=dev, dtype=x.dtype)
-        bflat = beta.detach().reshape(c).contiguous() if has_affine else torch.empty(0, device=dev, dtype=x.dtype)
+        has_affine, gflat, bflat = _flat_affine(gamma, beta, c, x)
 
         stats_sync = cfg.get("stats_sync", False) and use_batch
         world = 1
@@ -494,15 +505,9 @@ class _HipBatchNormMulti(torch.autograd.Function):
             if training and track and running_means is not None:
                 with torch.no_grad():
                     for p in range(parts):
-                        rm, rv = running_means[p], running_vars[p]
-                        mslice = mean[p * c:(p + 1) * c]
-                        vslice = var_unb[p * c:(p + 1) * c]
-                        if rm.dtype == torch.float32 and rm.is_contiguous() \
-                                and rv.dtype == torch.float32 and rv.is_contiguous():
-                            ext.ema_update(rm, mslice, rv, vslice, momentum)
-                        else:
-                            rm.mul_(1 - momentum).add_(mslice.to(rm.dtype), alpha=momentum)
-                            rv.mul_(1 - momentum).add_(vslice.to(rv.dtype), alpha=momentum)
+                        _ema_update(ext, running_means[p],
+                                    mean[p * c:(p + 1) * c], running_vars[p],
+                                    var_unb[p * c:(p + 1) * c], momentum)
         else:
             mean = torch.stack([_f32c(running_means[p]).reshape(c)
                                 for p in range(parts)]).reshape(-1).contiguous()

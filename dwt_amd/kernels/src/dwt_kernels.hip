@@ -988,7 +988,8 @@ __global__ void whiten_bwd_apply_kernel(
 // g x g accumulators live in registers):
 //   CW = min(C, 256) channels per z-slice, GW = CW/g groups per slice,
 //   thread t handles group (t % GW), position rows advance by 256/GW.
-//   Requires 256 % GW == 0 (C in {64,128,256,512,1024,2048} with g 2/4/8).
+//   Requires 256 % GW == 0 (C in {64,128,256,512,1024,2048} with g 2/4 —
+//   the only group sizes these kernels are instantiated for).
 // ===========================================================================
 
 template <typename T, int G>
@@ -1056,21 +1057,44 @@ template <> DEV_INLINE void store_group<c10::BFloat16, 8>(c10::BFloat16* p, cons
                  f32x2_to_bf16(i[4], i[5]), f32x2_to_bf16(i[6], i[7]));
 }
 
-// fused mean+cov, NHWC.  blockIdx.y = domain branch ("part"): x advances by
-// part*M*C and the per-part statistics are stacked ([parts, ...]) — one
-// launch covers all three domain branches of a norm site (launch-bound at
-// 7x7/14x14 otherwise; see profiles/norm_bench.md).
+// In every NHWC kernel blockIdx.y = domain branch ("part"): streamed tensors
+// advance by part*M*C (M = per-part N*H*W positions) and the per-part
+// statistics and parameters are stacked ([parts, ...]) — one launch covers all
+// three domain branches of a norm site (launch-bound at 7x7/14x14 otherwise;
+// see profiles/norm_bench.md).  Each kernel applies those offsets first.
+//
+// Lane map of the NHWC whitening kernels, shared by all of them:
+// blockIdx.z = 256-channel slice; in it lane t owns group slot t % GW
+// (channels c0..c0+G-1, global group grp) and the position rows
+// first_row(), first_row() + row_stride(), ... < M (evaluated at the loop,
+// after the parameter loads: the register allocation follows that order).
+template <int G>
+struct WhitenLanes {
+  int GW, slot, c0, grp, rows_per_iter, row_in_block;
+  DEV_INLINE WhitenLanes(int C, int part) {
+    const int CW = C < 256 ? C : 256;
+    GW = CW / G;
+    slot = threadIdx.x % GW;
+    c0 = blockIdx.z * 256 + (threadIdx.x % GW) * G;
+    grp = part * (C / G) + c0 / G;
+    rows_per_iter = blockDim.x / GW;
+    row_in_block = threadIdx.x / GW;
+  }
+  DEV_INLINE int64_t first_row() const {
+    return (int64_t)blockIdx.x * rows_per_iter + row_in_block;
+  }
+  DEV_INLINE int64_t row_stride() const {
+    return (int64_t)gridDim.x * rows_per_iter;
+  }
+};
+
+// fused mean+cov, NHWC
 template <typename T, int G>
 __global__ void whiten_stats_nhwc_kernel(
-    const T* __restrict__ x, float* __restrict__ acc,
-    int C, int64_t M /* = per-part N*H*W positions */) {
+    const T* __restrict__ x, float* __restrict__ acc, int C, int64_t M) {
   const int part = blockIdx.y;
   x += (int64_t)part * M * C;
-  const int CW = C < 256 ? C : 256;
-  const int GW = CW / G;
-  const int c0 = blockIdx.z * 256 + (threadIdx.x % GW) * G;
-  const int rows_per_iter = blockDim.x / GW;
-  const int row_in_block = threadIdx.x / GW;
+  const WhitenLanes<G> L(C, part);
 
   float s[G], p[G][G];
 #pragma unroll
@@ -1079,11 +1103,10 @@ __global__ void whiten_stats_nhwc_kernel(
 #pragma unroll
     for (int j = 0; j < G; ++j) p[i][j] = 0.f;
   }
-  const int64_t stride = (int64_t)gridDim.x * rows_per_iter;
-  for (int64_t m = (int64_t)blockIdx.x * rows_per_iter + row_in_block; m < M;
-       m += stride) {
+  const int64_t stride = L.row_stride();
+  for (int64_t m = L.first_row(); m < M; m += stride) {
     float v[G];
-    load_group<T, G>(x + m * C + c0, v);
+    load_group<T, G>(x + m * C + L.c0, v);
 #pragma unroll
     for (int i = 0; i < G; ++i) {
       s[i] += v[i];
@@ -1097,9 +1120,9 @@ __global__ void whiten_stats_nhwc_kernel(
   // atomic per value.
   constexpr int NTRI = G * (G + 1) / 2;
   __shared__ float lacc[(256 / G) * (G + NTRI)];  // [GW][G+NTRI], GW <= 256/G
-  float* mine = lacc + (threadIdx.x % GW) * (G + NTRI);
+  float* mine = lacc + L.slot * (G + NTRI);
   // zero once
-  for (int k = threadIdx.x; k < GW * (G + NTRI); k += blockDim.x) {
+  for (int k = threadIdx.x; k < L.GW * (G + NTRI); k += blockDim.x) {
     lacc[k] = 0.f;
   }
   __syncthreads();
@@ -1112,7 +1135,7 @@ __global__ void whiten_stats_nhwc_kernel(
       atomicAdd(&mine[G + i * (i + 1) / 2 + j], p[i][j]);
   __syncthreads();
   // first GW*(G+NTRI) threads flush to global
-  for (int k = threadIdx.x; k < GW * (G + NTRI); k += blockDim.x) {
+  for (int k = threadIdx.x; k < L.GW * (G + NTRI); k += blockDim.x) {
     const int lg = k / (G + NTRI);
     const int kk = k % (G + NTRI);
     const int gidx = part * (C / G) + blockIdx.z * (256 / G) + lg;
@@ -1128,38 +1151,38 @@ __global__ void whiten_stats_nhwc_kernel(
 }
 
 // fused apply, NHWC: fixed group per thread (W/params in registers),
-// positions advance additively — same CW/GW mapping as the stats kernel.
-template <typename T, int G>
+// positions advance additively.  RES fuses a block's residual join into its
+// last norm site: out = relu?(norm(x) + res), the add done in fp32 and
+// rounded once on the store, so the norm output is never materialised.  res
+// is one more streamed operand, offset per branch like x (unused if !RES).
+template <typename T, int G, bool RES>
 __global__ void whiten_apply_nhwc_kernel(
-    const T* __restrict__ x, const float* __restrict__ mean,
+    const T* __restrict__ x, const T* __restrict__ res,
+    const float* __restrict__ mean,
     const float* __restrict__ W, const T* __restrict__ gamma,
     const T* __restrict__ beta, T* __restrict__ out,
     int C, int64_t M, int relu, int has_affine) {
   const int part = blockIdx.y;
   x += (int64_t)part * M * C;
+  if constexpr (RES) res += (int64_t)part * M * C;
   out += (int64_t)part * M * C;
   mean += (int64_t)part * C;
-  const int CW = C < 256 ? C : 256;
-  const int GW = CW / G;
-  const int c0 = blockIdx.z * 256 + (threadIdx.x % GW) * G;
-  const int grp = part * (C / G) + c0 / G;
-  const int rows_per_iter = blockDim.x / GW;
-  const int row_in_block = threadIdx.x / GW;
-
+  const WhitenLanes<G> L(C, part);
   float m_[G], Wr[G][G], gm[G], bt[G];
 #pragma unroll
   for (int i = 0; i < G; ++i) {
-    m_[i] = mean[c0 + i];
-    gm[i] = has_affine ? ldf(gamma + c0 + i) : 1.f;
-    bt[i] = has_affine ? ldf(beta + c0 + i) : 0.f;
+    m_[i] = mean[L.c0 + i];
+    gm[i] = has_affine ? ldf(gamma + L.c0 + i) : 1.f;
+    bt[i] = has_affine ? ldf(beta + L.c0 + i) : 0.f;
 #pragma unroll
-    for (int j = 0; j < G; ++j) Wr[i][j] = W[((int64_t)grp * G + i) * G + j];
+    for (int j = 0; j < G; ++j) Wr[i][j] = W[((int64_t)L.grp * G + i) * G + j];
   }
-  const int64_t stride = (int64_t)gridDim.x * rows_per_iter;
-  for (int64_t m = (int64_t)blockIdx.x * rows_per_iter + row_in_block; m < M;
-       m += stride) {
+  const int64_t stride = L.row_stride();
+  for (int64_t m = L.first_row(); m < M; m += stride) {
+    [[maybe_unused]] float r[G];
     float v[G], y[G];
-    load_group<T, G>(x + m * C + c0, v);
+    load_group<T, G>(x + m * C + L.c0, v);
+    if constexpr (RES) load_group<T, G>(res + m * C + L.c0, r);
 #pragma unroll
     for (int j = 0; j < G; ++j) v[j] -= m_[j];
 #pragma unroll
@@ -1168,16 +1191,51 @@ __global__ void whiten_apply_nhwc_kernel(
 #pragma unroll
       for (int j = 0; j < G; ++j) a += Wr[i][j] * v[j];
       a = a * gm[i] + bt[i];
+      if constexpr (RES) a += r[i];
       y[i] = relu ? fmaxf(a, 0.f) : a;
     }
-    store_group<T, G>(out + m * C + c0, y);
+    store_group<T, G>(out + m * C + L.c0, y);
   }
 }
 
-// backward reduce, NHWC (same mapping as stats)
-template <typename T, int G>
+template <typename T> DEV_INLINE float round_to(float v);
+template <> DEV_INLINE float round_to<float>(float v) { return v; }
+template <> DEV_INLINE float round_to<c10::BFloat16>(float v) {
+  // same round-to-nearest-even as f32x2_to_bf16 (the store is then exact)
+  union { unsigned int u; float f; } x;
+  x.f = v;
+  x.u = (x.u + 0x7fffu + ((x.u >> 16) & 1u)) & 0xffff0000u;
+  return x.f;
+}
+
+// ga + gb of a JOIN backward reduce for one lane's V channels at off; gb may
+// be null (one consumer).
+template <typename T, int V>
+DEV_INLINE void join_sum(const T* __restrict__ ga, const T* __restrict__ gb,
+                         int64_t off, float* g) {
+  load_group<T, V>(ga + off, g);
+  if (gb) {
+    float t[V];
+    load_group<T, V>(gb + off, t);
+#pragma unroll
+    for (int j = 0; j < V; ++j) g[j] += t[j];
+  }
+}
+
+// backward reduce, NHWC.  Plain: the gradient is dout, masked by the relu of
+// the recomputed pre-activation.  JOIN: dout is ga and the gradient is
+// g = (ga + gb) * (y > 0), rounded to T and stored to gid (it is the
+// identity's gradient and the dout of the unchanged *_bwd_apply pass), while
+// the sums are accumulated from that ROUNDED value — exactly what a plain
+// reduce would read back.  y, gb, gid are unused otherwise; a join site has no
+// relu of its own, so relu and beta are unused then.  The two variants load
+// and address their operands in their own order (element offset shared in
+// JOIN, recomputed per operand in plain): the register allocation of the
+// bf16 instantiations follows that order, and it is kept as measured.
+template <typename T, int G, bool JOIN>
 __global__ void whiten_bwd_reduce_nhwc_kernel(
     const T* __restrict__ x, const T* __restrict__ dout,
+    const T* __restrict__ y, const T* __restrict__ gb, T* __restrict__ gid,
     const float* __restrict__ mean,
     const float* __restrict__ W, const T* __restrict__ gamma,
     const T* __restrict__ beta,
@@ -1186,23 +1244,23 @@ __global__ void whiten_bwd_reduce_nhwc_kernel(
   const int part = blockIdx.y;
   const int64_t poff = (int64_t)part * M * C;
   x += poff; dout += poff;
+  if constexpr (JOIN) {
+    y += poff; gid += poff;
+    if (gb) gb += poff;
+  }
   mean += (int64_t)part * C;
   dgb += (int64_t)part * 2 * C;
-  const int CW = C < 256 ? C : 256;
-  const int GW = CW / G;
-  const int c0 = blockIdx.z * 256 + (threadIdx.x % GW) * G;
-  const int grp = part * (C / G) + c0 / G;
-  const int rows_per_iter = blockDim.x / GW;
-  const int row_in_block = threadIdx.x / GW;
-
+  const WhitenLanes<G> L(C, part);
   float m_[G], Wr[G][G], gm[G], bt[G];
 #pragma unroll
   for (int i = 0; i < G; ++i) {
-    m_[i] = mean[c0 + i];
-    gm[i] = has_affine ? ldf(gamma + c0 + i) : 1.f;
-    bt[i] = has_affine ? ldf(beta + c0 + i) : 0.f;
+    m_[i] = mean[L.c0 + i];
+    gm[i] = has_affine ? ldf(gamma + L.c0 + i) : 1.f;
+    // beta is null in JOIN (no relu of the site's own to mask by)
+    if constexpr (JOIN) bt[i] = 0.f;
+    else bt[i] = has_affine ? ldf(beta + L.c0 + i) : 0.f;
 #pragma unroll
-    for (int j = 0; j < G; ++j) Wr[i][j] = W[((int64_t)grp * G + i) * G + j];
+    for (int j = 0; j < G; ++j) Wr[i][j] = W[((int64_t)L.grp * G + i) * G + j];
   }
   float dWl[G][G], dg[G], db[G];
 #pragma unroll
@@ -1211,23 +1269,38 @@ __global__ void whiten_bwd_reduce_nhwc_kernel(
 #pragma unroll
     for (int j = 0; j < G; ++j) dWl[i][j] = 0.f;
   }
-  const int64_t stride = (int64_t)gridDim.x * rows_per_iter;
-  for (int64_t m = (int64_t)blockIdx.x * rows_per_iter + row_in_block; m < M;
-       m += stride) {
+  const int64_t stride = L.row_stride();
+  for (int64_t m = L.first_row(); m < M; m += stride) {
     float xv[G], dyv[G];
-    load_group<T, G>(x + m * C + c0, xv);
-    load_group<T, G>(dout + m * C + c0, dyv);
+    if constexpr (JOIN) {
+      const int64_t off = m * C + L.c0;
+      float yv[G];
+      load_group<T, G>(x + off, xv);
+      load_group<T, G>(y + off, yv);
+      join_sum<T, G>(dout, gb, off, dyv);
 #pragma unroll
-    for (int j = 0; j < G; ++j) xv[j] -= m_[j];
+      for (int j = 0; j < G; ++j) {
+        dyv[j] = yv[j] > 0.f ? round_to<T>(dyv[j]) : 0.f;
+        xv[j] -= m_[j];
+      }
+      store_group<T, G>(gid + off, dyv);
+    } else {
+      load_group<T, G>(x + m * C + L.c0, xv);
+      load_group<T, G>(dout + m * C + L.c0, dyv);
+#pragma unroll
+      for (int j = 0; j < G; ++j) xv[j] -= m_[j];
+    }
 #pragma unroll
     for (int i = 0; i < G; ++i) {
       float y0 = 0.f;
 #pragma unroll
       for (int j = 0; j < G; ++j) y0 += Wr[i][j] * xv[j];
-      // relu mask recomputed from the same fp32 pre-activation the forward
-      // stored (bf16 rounding preserves sign) — saves the out re-read
       float dy = dyv[i];
-      if (relu && gm[i] * y0 + bt[i] <= 0.f) dy = 0.f;
+      if constexpr (!JOIN) {
+        // relu mask recomputed from the same fp32 pre-activation the forward
+        // stored (bf16 rounding preserves sign) — saves the out re-read
+        if (relu && gm[i] * y0 + bt[i] <= 0.f) dy = 0.f;
+      }
       db[i] += dy;
       dg[i] += dy * y0;
       const float dy0 = dy * gm[i];
@@ -1238,8 +1311,8 @@ __global__ void whiten_bwd_reduce_nhwc_kernel(
   // per-block LDS accumulate by group slot, then one global atomic per value
   constexpr int NV = 2 * G + G * G;
   __shared__ float lacc[(256 / G) * NV];  // [GW][NV], GW <= 256/G
-  float* mine = lacc + (threadIdx.x % GW) * NV;
-  for (int k = threadIdx.x; k < GW * NV; k += blockDim.x) lacc[k] = 0.f;
+  float* mine = lacc + L.slot * NV;
+  for (int k = threadIdx.x; k < L.GW * NV; k += blockDim.x) lacc[k] = 0.f;
   __syncthreads();
 #pragma unroll
   for (int i = 0; i < G; ++i) {
@@ -1249,7 +1322,7 @@ __global__ void whiten_bwd_reduce_nhwc_kernel(
     for (int j = 0; j < G; ++j) atomicAdd(&mine[2 * G + i * G + j], dWl[i][j]);
   }
   __syncthreads();
-  for (int k = threadIdx.x; k < GW * NV; k += blockDim.x) {
+  for (int k = threadIdx.x; k < L.GW * NV; k += blockDim.x) {
     const int lg = k / NV;
     const int kk = k % NV;
     const int lgidx = blockIdx.z * (256 / G) + lg;      // group within part
@@ -1276,33 +1349,26 @@ __global__ void whiten_bwd_apply_nhwc_kernel(
   x += poff; dout += poff; dx += poff;
   mean += (int64_t)part * C;
   if (train_stats) corr += (int64_t)part * C;  // empty tensor in eval
-  const int CW = C < 256 ? C : 256;
-  const int GW = CW / G;
-  const int c0 = blockIdx.z * 256 + (threadIdx.x % GW) * G;
-  const int grp = part * (C / G) + c0 / G;
-  const int rows_per_iter = blockDim.x / GW;
-  const int row_in_block = threadIdx.x / GW;
-
+  const WhitenLanes<G> L(C, part);
   float m_[G], Wt[G][G], Wr[G][G], Sr[G][G], gm[G], bt[G], cr[G];
 #pragma unroll
   for (int i = 0; i < G; ++i) {
-    m_[i] = mean[c0 + i];
-    gm[i] = has_affine ? ldf(gamma + c0 + i) : 1.f;
-    bt[i] = has_affine ? ldf(beta + c0 + i) : 0.f;
-    cr[i] = train_stats ? corr[c0 + i] : 0.f;
+    m_[i] = mean[L.c0 + i];
+    gm[i] = has_affine ? ldf(gamma + L.c0 + i) : 1.f;
+    bt[i] = has_affine ? ldf(beta + L.c0 + i) : 0.f;
+    cr[i] = train_stats ? corr[L.c0 + i] : 0.f;
 #pragma unroll
     for (int j = 0; j < G; ++j) {
-      Wr[i][j] = W[((int64_t)grp * G + i) * G + j];
-      Wt[i][j] = W[((int64_t)grp * G + j) * G + i];  // W^T
-      Sr[i][j] = train_stats ? S[((int64_t)grp * G + i) * G + j] : 0.f;
+      Wr[i][j] = W[((int64_t)L.grp * G + i) * G + j];
+      Wt[i][j] = W[((int64_t)L.grp * G + j) * G + i];  // W^T
+      Sr[i][j] = train_stats ? S[((int64_t)L.grp * G + i) * G + j] : 0.f;
     }
   }
-  const int64_t stride = (int64_t)gridDim.x * rows_per_iter;
-  for (int64_t m = (int64_t)blockIdx.x * rows_per_iter + row_in_block; m < M;
-       m += stride) {
+  const int64_t stride = L.row_stride();
+  for (int64_t m = L.first_row(); m < M; m += stride) {
     float xv[G], dyv[G], r[G];
-    load_group<T, G>(x + m * C + c0, xv);
-    load_group<T, G>(dout + m * C + c0, dyv);
+    load_group<T, G>(x + m * C + L.c0, xv);
+    load_group<T, G>(dout + m * C + L.c0, dyv);
 #pragma unroll
     for (int j = 0; j < G; ++j) xv[j] -= m_[j];
     if (relu) {
@@ -1323,148 +1389,176 @@ __global__ void whiten_bwd_apply_nhwc_kernel(
       for (int j = 0; j < G; ++j) a += Wt[i][j] * dyv[j] + Sr[i][j] * xv[j];
       r[i] = a;
     }
-    store_group<T, G>(dx + m * C + c0, r);
+    store_group<T, G>(dx + m * C + L.c0, r);
   }
 }
 
-// BN NHWC: per-lane 4-channel chunks.  blockIdx.y = domain branch, as in the
-// whitening NHWC family (acc/sums/mean/istd stacked [parts, ...]).
+// Lane map of the NHWC BN kernels: per-lane VC-channel chunks.  blockIdx.y =
+// domain branch as in the whitening family (acc/sums/mean/istd stacked
+// [parts, ...]); blockIdx.z = 1024-channel slice of CW channels, in which
+// lane t owns channels c0..c0+VC-1 and rows as in WhitenLanes.
+struct BnLanes {
+  static constexpr int VC = 4;
+  int CW, c0, rows_per_iter, row_in_block;
+  DEV_INLINE explicit BnLanes(int C) {
+    CW = C < 1024 ? C : 1024;
+    const int NCH = CW / VC;
+    c0 = blockIdx.z * 1024 + (threadIdx.x % NCH) * VC;
+    rows_per_iter = blockDim.x / NCH;
+    row_in_block = threadIdx.x / NCH;
+  }
+  DEV_INLINE int64_t first_row() const {
+    return (int64_t)blockIdx.x * rows_per_iter + row_in_block;
+  }
+  DEV_INLINE int64_t row_stride() const {
+    return (int64_t)gridDim.x * rows_per_iter;
+  }
+};
+
+// Two per-lane sums per channel into this part's acc[2][C]: per-block LDS
+// accumulation -> one global atomic per channel per block.
+DEV_INLINE void bn_two_sum_flush(const BnLanes& L, int C,
+                                 const float (&a)[BnLanes::VC],
+                                 const float (&b)[BnLanes::VC],
+                                 float* __restrict__ acc /* this part's */) {
+  __shared__ float lacc[2 * 1024];
+  const int cb = L.c0 - blockIdx.z * 1024;
+  for (int k = threadIdx.x; k < 2 * L.CW; k += blockDim.x) lacc[k] = 0.f;
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < BnLanes::VC; ++k) {
+    atomicAdd(&lacc[cb + k], a[k]);
+    atomicAdd(&lacc[L.CW + cb + k], b[k]);
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < L.CW; k += blockDim.x) {
+    atomicAdd(&acc[blockIdx.z * 1024 + k], lacc[k]);
+    atomicAdd(&acc[C + blockIdx.z * 1024 + k], lacc[L.CW + k]);
+  }
+}
+
 template <typename T>
 __global__ void bn_stats_nhwc_kernel(
     const T* __restrict__ x, float* __restrict__ acc, int C, int64_t M) {
+  constexpr int VC = BnLanes::VC;
   const int part = blockIdx.y;
   x += (int64_t)part * M * C;
   acc += (int64_t)part * 2 * C;
-  constexpr int VC = 4;
-  const int CW = C < 1024 ? C : 1024;
-  const int NCH = CW / VC;
-  const int c0 = blockIdx.z * 1024 + (threadIdx.x % NCH) * VC;
-  const int rows_per_iter = blockDim.x / NCH;
-  const int row_in_block = threadIdx.x / NCH;
+  const BnLanes L(C);
   float s[VC], ss[VC];
 #pragma unroll
   for (int k = 0; k < VC; ++k) { s[k] = 0.f; ss[k] = 0.f; }
-  const int64_t stride = (int64_t)gridDim.x * rows_per_iter;
-  for (int64_t m = (int64_t)blockIdx.x * rows_per_iter + row_in_block; m < M;
-       m += stride) {
+  const int64_t stride = L.row_stride();
+  for (int64_t m = L.first_row(); m < M; m += stride) {
     float v[VC];
-    load_group<T, VC>(x + m * C + c0, v);
+    load_group<T, VC>(x + m * C + L.c0, v);
 #pragma unroll
     for (int k = 0; k < VC; ++k) { s[k] += v[k]; ss[k] += v[k] * v[k]; }
   }
-  // per-block LDS accumulation -> one global atomic per channel per block
-  __shared__ float lacc[2 * 1024];
-  const int cb = c0 - blockIdx.z * 1024;
-  for (int k = threadIdx.x; k < 2 * CW; k += blockDim.x) lacc[k] = 0.f;
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < VC; ++k) {
-    atomicAdd(&lacc[cb + k], s[k]);
-    atomicAdd(&lacc[CW + cb + k], ss[k]);
-  }
-  __syncthreads();
-  for (int k = threadIdx.x; k < CW; k += blockDim.x) {
-    atomicAdd(&acc[blockIdx.z * 1024 + k], lacc[k]);
-    atomicAdd(&acc[C + blockIdx.z * 1024 + k], lacc[CW + k]);
-  }
+  bn_two_sum_flush(L, C, s, ss, acc);
 }
 
-template <typename T>
+// RES: the residual join of the block's last norm site, as in
+// whiten_apply_nhwc_kernel
+template <typename T, bool RES>
 __global__ void bn_apply_nhwc_kernel(
-    const T* __restrict__ x, const float* __restrict__ mean,
+    const T* __restrict__ x, const T* __restrict__ res,
+    const float* __restrict__ mean,
     const float* __restrict__ istd, const T* __restrict__ gamma,
     const T* __restrict__ beta, T* __restrict__ out, int C, int64_t M,
     int relu, int has_affine) {
+  constexpr int VC = BnLanes::VC;
   const int part = blockIdx.y;
   x += (int64_t)part * M * C;
+  if constexpr (RES) res += (int64_t)part * M * C;
   out += (int64_t)part * M * C;
   mean += (int64_t)part * C;
   istd += (int64_t)part * C;
-  constexpr int VC = 4;
-  const int CW = C < 1024 ? C : 1024;
-  const int NCH = CW / VC;
-  const int c0 = blockIdx.z * 1024 + (threadIdx.x % NCH) * VC;
-  const int rows_per_iter = blockDim.x / NCH;
-  const int row_in_block = threadIdx.x / NCH;
+  const BnLanes L(C);
   float mu[VC], is[VC], gm[VC], bt[VC];
 #pragma unroll
   for (int k = 0; k < VC; ++k) {
-    mu[k] = mean[c0 + k];
-    is[k] = istd[c0 + k];
-    gm[k] = has_affine ? ldf(gamma + c0 + k) : 1.f;
-    bt[k] = has_affine ? ldf(beta + c0 + k) : 0.f;
+    mu[k] = mean[L.c0 + k];
+    is[k] = istd[L.c0 + k];
+    gm[k] = has_affine ? ldf(gamma + L.c0 + k) : 1.f;
+    bt[k] = has_affine ? ldf(beta + L.c0 + k) : 0.f;
   }
-  const int64_t stride = (int64_t)gridDim.x * rows_per_iter;
-  for (int64_t m = (int64_t)blockIdx.x * rows_per_iter + row_in_block; m < M;
-       m += stride) {
+  const int64_t stride = L.row_stride();
+  for (int64_t m = L.first_row(); m < M; m += stride) {
+    [[maybe_unused]] float r[VC];
     float v[VC];
-    load_group<T, VC>(x + m * C + c0, v);
+    load_group<T, VC>(x + m * C + L.c0, v);
+    if constexpr (RES) load_group<T, VC>(res + m * C + L.c0, r);
 #pragma unroll
     for (int k = 0; k < VC; ++k) {
-      const float y = (v[k] - mu[k]) * is[k] * gm[k] + bt[k];
+      float y = (v[k] - mu[k]) * is[k] * gm[k] + bt[k];
+      if constexpr (RES) y += r[k];
       v[k] = relu ? fmaxf(y, 0.f) : y;
     }
-    store_group<T, VC>(out + m * C + c0, v);
+    store_group<T, VC>(out + m * C + L.c0, v);
   }
 }
 
-template <typename T>
+// Plain / JOIN as in whiten_bwd_reduce_nhwc_kernel (JOIN: dout is ga; gamma,
+// beta and relu are unused)
+template <typename T, bool JOIN>
 __global__ void bn_bwd_reduce_nhwc_kernel(
     const T* __restrict__ x, const T* __restrict__ dout,
+    const T* __restrict__ y, const T* __restrict__ gb, T* __restrict__ gid,
     const float* __restrict__ mean,
     const float* __restrict__ istd, const T* __restrict__ gamma,
     const T* __restrict__ beta, float* __restrict__ sums, int C,
     int64_t M, int relu, int has_affine) {
+  constexpr int VC = BnLanes::VC;
   const int part = blockIdx.y;
   const int64_t poff = (int64_t)part * M * C;
   x += poff; dout += poff;
+  if constexpr (JOIN) {
+    y += poff; gid += poff;
+    if (gb) gb += poff;
+  }
   mean += (int64_t)part * C;
   istd += (int64_t)part * C;
   sums += (int64_t)part * 2 * C;
-  constexpr int VC = 4;
-  const int CW = C < 1024 ? C : 1024;
-  const int NCH = CW / VC;
-  const int c0 = blockIdx.z * 1024 + (threadIdx.x % NCH) * VC;
-  const int rows_per_iter = blockDim.x / NCH;
-  const int row_in_block = threadIdx.x / NCH;
-  float s_dy[VC], s_dyxh[VC], mu[VC], is[VC], gm[VC], bt[VC];
+  const BnLanes L(C);
+  float mu[VC], is[VC], gm[VC], bt[VC];
 #pragma unroll
   for (int k = 0; k < VC; ++k) {
-    s_dy[k] = 0.f; s_dyxh[k] = 0.f;
-    mu[k] = mean[c0 + k];
-    is[k] = istd[c0 + k];
-    gm[k] = has_affine ? ldf(gamma + c0 + k) : 1.f;
-    bt[k] = has_affine ? ldf(beta + c0 + k) : 0.f;
+    mu[k] = mean[L.c0 + k];
+    is[k] = istd[L.c0 + k];
+    gm[k] = has_affine ? ldf(gamma + L.c0 + k) : 1.f;
+    bt[k] = has_affine ? ldf(beta + L.c0 + k) : 0.f;
   }
-  const int64_t stride = (int64_t)gridDim.x * rows_per_iter;
-  for (int64_t m = (int64_t)blockIdx.x * rows_per_iter + row_in_block; m < M;
-       m += stride) {
+  float s_dy[VC], s_dyxh[VC];
+#pragma unroll
+  for (int k = 0; k < VC; ++k) { s_dy[k] = 0.f; s_dyxh[k] = 0.f; }
+  const int64_t stride = L.row_stride();
+  for (int64_t m = L.first_row(); m < M; m += stride) {
+    [[maybe_unused]] const int64_t off = m * C + L.c0;  // JOIN's addressing
+    [[maybe_unused]] float yv[VC];
     float xv[VC], dv[VC];
-    load_group<T, VC>(x + m * C + c0, xv);
-    load_group<T, VC>(dout + m * C + c0, dv);
+    if constexpr (JOIN) {
+      load_group<T, VC>(x + off, xv);
+      load_group<T, VC>(y + off, yv);
+      join_sum<T, VC>(dout, gb, off, dv);
+    } else {
+      load_group<T, VC>(x + m * C + L.c0, xv);
+      load_group<T, VC>(dout + m * C + L.c0, dv);
+    }
 #pragma unroll
     for (int k = 0; k < VC; ++k) {
+      if constexpr (JOIN) dv[k] = yv[k] > 0.f ? round_to<T>(dv[k]) : 0.f;
       const float xh = (xv[k] - mu[k]) * is[k];
-      // relu mask recomputed (sign survives the forward's bf16 store)
-      if (relu && gm[k] * xh + bt[k] <= 0.f) dv[k] = 0.f;
+      if constexpr (!JOIN) {
+        // relu mask recomputed (sign survives the forward's bf16 store)
+        if (relu && gm[k] * xh + bt[k] <= 0.f) dv[k] = 0.f;
+      }
       s_dy[k] += dv[k];
       s_dyxh[k] += dv[k] * xh;
     }
+    if constexpr (JOIN) store_group<T, VC>(gid + off, dv);
   }
-  __shared__ float lacc[2 * 1024];
-  const int cb = c0 - blockIdx.z * 1024;
-  for (int k = threadIdx.x; k < 2 * CW; k += blockDim.x) lacc[k] = 0.f;
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < VC; ++k) {
-    atomicAdd(&lacc[cb + k], s_dy[k]);
-    atomicAdd(&lacc[CW + cb + k], s_dyxh[k]);
-  }
-  __syncthreads();
-  for (int k = threadIdx.x; k < CW; k += blockDim.x) {
-    atomicAdd(&sums[blockIdx.z * 1024 + k], lacc[k]);
-    atomicAdd(&sums[C + blockIdx.z * 1024 + k], lacc[CW + k]);
-  }
+  bn_two_sum_flush(L, C, s_dy, s_dyxh, sums);
 }
 
 template <typename T>
@@ -1475,22 +1569,18 @@ __global__ void bn_bwd_apply_nhwc_kernel(
     const T* __restrict__ beta,
     const float* __restrict__ sums, T* __restrict__ dx, int C, int64_t M,
     float inv_m, int relu, int has_affine, int use_batch) {
+  constexpr int VC = BnLanes::VC;
   const int part = blockIdx.y;
   const int64_t poff = (int64_t)part * M * C;
   x += poff; dout += poff; dx += poff;
   mean += (int64_t)part * C;
   istd += (int64_t)part * C;
   sums += (int64_t)part * 2 * C;
-  constexpr int VC = 4;
-  const int CW = C < 1024 ? C : 1024;
-  const int NCH = CW / VC;
-  const int c0 = blockIdx.z * 1024 + (threadIdx.x % NCH) * VC;
-  const int rows_per_iter = blockDim.x / NCH;
-  const int row_in_block = threadIdx.x / NCH;
+  const BnLanes L(C);
   float mu[VC], is[VC], gm[VC], bt[VC], mdy[VC], mdyxh[VC];
 #pragma unroll
   for (int k = 0; k < VC; ++k) {
-    const int c = c0 + k;
+    const int c = L.c0 + k;
     mu[k] = mean[c];
     is[k] = istd[c];
     gm[k] = has_affine ? ldf(gamma + c) : 1.f;
@@ -1498,12 +1588,11 @@ __global__ void bn_bwd_apply_nhwc_kernel(
     mdy[k] = use_batch ? sums[c] * inv_m : 0.f;
     mdyxh[k] = use_batch ? sums[C + c] * inv_m : 0.f;
   }
-  const int64_t stride = (int64_t)gridDim.x * rows_per_iter;
-  for (int64_t m = (int64_t)blockIdx.x * rows_per_iter + row_in_block; m < M;
-       m += stride) {
+  const int64_t stride = L.row_stride();
+  for (int64_t m = L.first_row(); m < M; m += stride) {
     float xv[VC], dv[VC];
-    load_group<T, VC>(x + m * C + c0, xv);
-    load_group<T, VC>(dout + m * C + c0, dv);
+    load_group<T, VC>(x + m * C + L.c0, xv);
+    load_group<T, VC>(dout + m * C + L.c0, dv);
 #pragma unroll
     for (int k = 0; k < VC; ++k) {
       const float xh = (xv[k] - mu[k]) * is[k];
@@ -1515,282 +1604,7 @@ __global__ void bn_bwd_apply_nhwc_kernel(
         dv[k] = dxh * is[k];
       }
     }
-    store_group<T, VC>(dx + m * C + c0, dv);
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Residual join fused into a block's last norm site (NHWC).
-//
-// Forward:  out = relu?(norm(x) + res) — the add is done in fp32 and rounded
-// once on the store, so the norm output is never materialised.  These are
-// siblings of the plain apply kernels (which stay untouched: same code, same
-// register counts) with one extra streamed operand, offset per branch like x.
-//
-// Backward: g = (ga + gb) * (y > 0), rounded to T and stored to gid (it is
-// the identity's gradient and the dout of the unchanged *_bwd_apply pass),
-// while the reduce sums are accumulated from that ROUNDED value — exactly
-// what the plain reduce would read back.  gb may be null (one consumer).
-// Lane mapping, branch offsets and LDS/atomic epilogue are those of the
-// plain *_bwd_reduce_nhwc kernels.
-// ---------------------------------------------------------------------------
-
-template <typename T> DEV_INLINE float round_to(float v);
-template <> DEV_INLINE float round_to<float>(float v) { return v; }
-template <> DEV_INLINE float round_to<c10::BFloat16>(float v) {
-  // same round-to-nearest-even as f32x2_to_bf16 (the store is then exact)
-  union { unsigned int u; float f; } x;
-  x.f = v;
-  x.u = (x.u + 0x7fffu + ((x.u >> 16) & 1u)) & 0xffff0000u;
-  return x.f;
-}
-
-template <typename T, int G>
-__global__ void whiten_apply_res_nhwc_kernel(
-    const T* __restrict__ x, const T* __restrict__ res,
-    const float* __restrict__ mean,
-    const float* __restrict__ W, const T* __restrict__ gamma,
-    const T* __restrict__ beta, T* __restrict__ out,
-    int C, int64_t M, int relu, int has_affine) {
-  const int part = blockIdx.y;
-  x += (int64_t)part * M * C;
-  res += (int64_t)part * M * C;
-  out += (int64_t)part * M * C;
-  mean += (int64_t)part * C;
-  const int CW = C < 256 ? C : 256;
-  const int GW = CW / G;
-  const int c0 = blockIdx.z * 256 + (threadIdx.x % GW) * G;
-  const int grp = part * (C / G) + c0 / G;
-  const int rows_per_iter = blockDim.x / GW;
-  const int row_in_block = threadIdx.x / GW;
-
-  float m_[G], Wr[G][G], gm[G], bt[G];
-#pragma unroll
-  for (int i = 0; i < G; ++i) {
-    m_[i] = mean[c0 + i];
-    gm[i] = has_affine ? ldf(gamma + c0 + i) : 1.f;
-    bt[i] = has_affine ? ldf(beta + c0 + i) : 0.f;
-#pragma unroll
-    for (int j = 0; j < G; ++j) Wr[i][j] = W[((int64_t)grp * G + i) * G + j];
-  }
-  const int64_t stride = (int64_t)gridDim.x * rows_per_iter;
-  for (int64_t m = (int64_t)blockIdx.x * rows_per_iter + row_in_block; m < M;
-       m += stride) {
-    float v[G], r[G], y[G];
-    load_group<T, G>(x + m * C + c0, v);
-    load_group<T, G>(res + m * C + c0, r);
-#pragma unroll
-    for (int j = 0; j < G; ++j) v[j] -= m_[j];
-#pragma unroll
-    for (int i = 0; i < G; ++i) {
-      float a = 0.f;
-#pragma unroll
-      for (int j = 0; j < G; ++j) a += Wr[i][j] * v[j];
-      a = a * gm[i] + bt[i] + r[i];
-      y[i] = relu ? fmaxf(a, 0.f) : a;
-    }
-    store_group<T, G>(out + m * C + c0, y);
-  }
-}
-
-template <typename T>
-__global__ void bn_apply_res_nhwc_kernel(
-    const T* __restrict__ x, const T* __restrict__ res,
-    const float* __restrict__ mean,
-    const float* __restrict__ istd, const T* __restrict__ gamma,
-    const T* __restrict__ beta, T* __restrict__ out, int C, int64_t M,
-    int relu, int has_affine) {
-  const int part = blockIdx.y;
-  x += (int64_t)part * M * C;
-  res += (int64_t)part * M * C;
-  out += (int64_t)part * M * C;
-  mean += (int64_t)part * C;
-  istd += (int64_t)part * C;
-  constexpr int VC = 4;
-  const int CW = C < 1024 ? C : 1024;
-  const int NCH = CW / VC;
-  const int c0 = blockIdx.z * 1024 + (threadIdx.x % NCH) * VC;
-  const int rows_per_iter = blockDim.x / NCH;
-  const int row_in_block = threadIdx.x / NCH;
-  float mu[VC], is[VC], gm[VC], bt[VC];
-#pragma unroll
-  for (int k = 0; k < VC; ++k) {
-    mu[k] = mean[c0 + k];
-    is[k] = istd[c0 + k];
-    gm[k] = has_affine ? ldf(gamma + c0 + k) : 1.f;
-    bt[k] = has_affine ? ldf(beta + c0 + k) : 0.f;
-  }
-  const int64_t stride = (int64_t)gridDim.x * rows_per_iter;
-  for (int64_t m = (int64_t)blockIdx.x * rows_per_iter + row_in_block; m < M;
-       m += stride) {
-    float v[VC], r[VC];
-    load_group<T, VC>(x + m * C + c0, v);
-    load_group<T, VC>(res + m * C + c0, r);
-#pragma unroll
-    for (int k = 0; k < VC; ++k) {
-      const float y = (v[k] - mu[k]) * is[k] * gm[k] + bt[k] + r[k];
-      v[k] = relu ? fmaxf(y, 0.f) : y;
-    }
-    store_group<T, VC>(out + m * C + c0, v);
-  }
-}
-
-template <typename T, int G>
-__global__ void whiten_join_bwd_reduce_nhwc_kernel(
-    const T* __restrict__ x, const T* __restrict__ y,
-    const T* __restrict__ ga, const T* __restrict__ gb /* may be null */,
-    const float* __restrict__ mean, const float* __restrict__ W,
-    const T* __restrict__ gamma, T* __restrict__ gid,
-    float* __restrict__ dWacc, float* __restrict__ dgb,
-    int C, int64_t M, int has_affine) {
-  const int part = blockIdx.y;
-  const int64_t poff = (int64_t)part * M * C;
-  x += poff; y += poff; ga += poff; gid += poff;
-  if (gb) gb += poff;
-  mean += (int64_t)part * C;
-  dgb += (int64_t)part * 2 * C;
-  const int CW = C < 256 ? C : 256;
-  const int GW = CW / G;
-  const int c0 = blockIdx.z * 256 + (threadIdx.x % GW) * G;
-  const int grp = part * (C / G) + c0 / G;
-  const int rows_per_iter = blockDim.x / GW;
-  const int row_in_block = threadIdx.x / GW;
-
-  float m_[G], Wr[G][G], gm[G];
-#pragma unroll
-  for (int i = 0; i < G; ++i) {
-    m_[i] = mean[c0 + i];
-    gm[i] = has_affine ? ldf(gamma + c0 + i) : 1.f;
-#pragma unroll
-    for (int j = 0; j < G; ++j) Wr[i][j] = W[((int64_t)grp * G + i) * G + j];
-  }
-  float dWl[G][G], dg[G], db[G];
-#pragma unroll
-  for (int i = 0; i < G; ++i) {
-    dg[i] = 0.f; db[i] = 0.f;
-#pragma unroll
-    for (int j = 0; j < G; ++j) dWl[i][j] = 0.f;
-  }
-  const int64_t stride = (int64_t)gridDim.x * rows_per_iter;
-  for (int64_t m = (int64_t)blockIdx.x * rows_per_iter + row_in_block; m < M;
-       m += stride) {
-    const int64_t off = m * C + c0;
-    float xv[G], yv[G], dyv[G];
-    load_group<T, G>(x + off, xv);
-    load_group<T, G>(y + off, yv);
-    load_group<T, G>(ga + off, dyv);
-    if (gb) {
-      float t[G];
-      load_group<T, G>(gb + off, t);
-#pragma unroll
-      for (int j = 0; j < G; ++j) dyv[j] += t[j];
-    }
-#pragma unroll
-    for (int j = 0; j < G; ++j) {
-      dyv[j] = yv[j] > 0.f ? round_to<T>(dyv[j]) : 0.f;
-      xv[j] -= m_[j];
-    }
-    store_group<T, G>(gid + off, dyv);
-#pragma unroll
-    for (int i = 0; i < G; ++i) {
-      float y0 = 0.f;
-#pragma unroll
-      for (int j = 0; j < G; ++j) y0 += Wr[i][j] * xv[j];
-      const float dy = dyv[i];
-      db[i] += dy;
-      dg[i] += dy * y0;
-      const float dy0 = dy * gm[i];
-#pragma unroll
-      for (int j = 0; j < G; ++j) dWl[i][j] += dy0 * xv[j];
-    }
-  }
-  constexpr int NV = 2 * G + G * G;
-  __shared__ float lacc[(256 / G) * NV];  // [GW][NV], GW <= 256/G
-  float* mine = lacc + (threadIdx.x % GW) * NV;
-  for (int k = threadIdx.x; k < GW * NV; k += blockDim.x) lacc[k] = 0.f;
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < G; ++i) {
-    atomicAdd(&mine[i], dg[i]);
-    atomicAdd(&mine[G + i], db[i]);
-#pragma unroll
-    for (int j = 0; j < G; ++j) atomicAdd(&mine[2 * G + i * G + j], dWl[i][j]);
-  }
-  __syncthreads();
-  for (int k = threadIdx.x; k < GW * NV; k += blockDim.x) {
-    const int lg = k / NV;
-    const int kk = k % NV;
-    const int lgidx = blockIdx.z * (256 / G) + lg;      // group within part
-    const int gidx = part * (C / G) + lgidx;            // global group
-    const int cg0 = lgidx * G;
-    if (kk < G) atomicAdd(&dgb[cg0 + kk], lacc[k]);
-    else if (kk < 2 * G) atomicAdd(&dgb[C + cg0 + (kk - G)], lacc[k]);
-    else atomicAdd(&dWacc[(int64_t)gidx * G * G + (kk - 2 * G)], lacc[k]);
-  }
-}
-
-template <typename T>
-__global__ void bn_join_bwd_reduce_nhwc_kernel(
-    const T* __restrict__ x, const T* __restrict__ y,
-    const T* __restrict__ ga, const T* __restrict__ gb /* may be null */,
-    const float* __restrict__ mean, const float* __restrict__ istd,
-    T* __restrict__ gid, float* __restrict__ sums, int C, int64_t M) {
-  const int part = blockIdx.y;
-  const int64_t poff = (int64_t)part * M * C;
-  x += poff; y += poff; ga += poff; gid += poff;
-  if (gb) gb += poff;
-  mean += (int64_t)part * C;
-  istd += (int64_t)part * C;
-  sums += (int64_t)part * 2 * C;
-  constexpr int VC = 4;
-  const int CW = C < 1024 ? C : 1024;
-  const int NCH = CW / VC;
-  const int c0 = blockIdx.z * 1024 + (threadIdx.x % NCH) * VC;
-  const int rows_per_iter = blockDim.x / NCH;
-  const int row_in_block = threadIdx.x / NCH;
-  float s_dy[VC], s_dyxh[VC], mu[VC], is[VC];
-#pragma unroll
-  for (int k = 0; k < VC; ++k) {
-    s_dy[k] = 0.f; s_dyxh[k] = 0.f;
-    mu[k] = mean[c0 + k];
-    is[k] = istd[c0 + k];
-  }
-  const int64_t stride = (int64_t)gridDim.x * rows_per_iter;
-  for (int64_t m = (int64_t)blockIdx.x * rows_per_iter + row_in_block; m < M;
-       m += stride) {
-    const int64_t off = m * C + c0;
-    float xv[VC], yv[VC], dv[VC];
-    load_group<T, VC>(x + off, xv);
-    load_group<T, VC>(y + off, yv);
-    load_group<T, VC>(ga + off, dv);
-    if (gb) {
-      float t[VC];
-      load_group<T, VC>(gb + off, t);
-#pragma unroll
-      for (int k = 0; k < VC; ++k) dv[k] += t[k];
-    }
-#pragma unroll
-    for (int k = 0; k < VC; ++k) {
-      dv[k] = yv[k] > 0.f ? round_to<T>(dv[k]) : 0.f;
-      const float xh = (xv[k] - mu[k]) * is[k];
-      s_dy[k] += dv[k];
-      s_dyxh[k] += dv[k] * xh;
-    }
-    store_group<T, VC>(gid + off, dv);
-  }
-  __shared__ float lacc[2 * 1024];
-  const int cb = c0 - blockIdx.z * 1024;
-  for (int k = threadIdx.x; k < 2 * CW; k += blockDim.x) lacc[k] = 0.f;
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < VC; ++k) {
-    atomicAdd(&lacc[cb + k], s_dy[k]);
-    atomicAdd(&lacc[CW + cb + k], s_dyxh[k]);
-  }
-  __syncthreads();
-  for (int k = threadIdx.x; k < CW; k += blockDim.x) {
-    atomicAdd(&sums[blockIdx.z * 1024 + k], lacc[k]);
-    atomicAdd(&sums[C + blockIdx.z * 1024 + k], lacc[CW + k]);
+    store_group<T, VC>(dx + m * C + L.c0, dv);
   }
 }
 
@@ -2507,11 +2321,12 @@ void whiten_stats(Tensor x, Tensor acc, Tensor mean, Tensor cov, int64_t g) {
 // ---------------------- NHWC (channels_last) launchers -------------------
 // x is the raw NHWC storage; M = N*H*W positions, C channels.
 
+// Group sizes 2 and 4 only — the NHWC route never takes g=8 (it spills; see
+// hip_ops.whiten_cl_supported).
 #define DWT_SWITCH_G(g, body)                                                  \
   switch (g) {                                                                 \
     case 2: { constexpr int G = 2; body; break; }                              \
     case 4: { constexpr int G = 4; body; break; }                              \
-    case 8: { constexpr int G = 8; body; break; }                              \
     default: TORCH_CHECK(false, "unsupported group size ", g);                 \
   }
 
@@ -2521,19 +2336,54 @@ inline int64_t nhwc_reduce_blocks(int64_t M, int rows_per_iter, int zslices) {
   return std::min(std::max<int64_t>(want, 1), cap);
 }
 
+inline int64_t nhwc_elem_blocks(int64_t M, int rows_per_iter, int zslices) {
+  const int64_t want = (M + rows_per_iter - 1) / rows_per_iter;
+  const int64_t cap = std::max<int64_t>(1, 8192 / std::max(zslices, 1));
+  return std::min(std::max<int64_t>(want, 1), cap);
+}
+
+// Grid of a 256-thread NHWC kernel (see WhitenLanes / BnLanes): x = blocks of
+// position rows, y = parts, z = slices of `slice` channels, each row of a
+// slice taking min(C, slice) / vec lanes.
+inline dim3 nhwc_grid(bool reduce, int64_t C, int64_t M, int64_t parts,
+                      int slice, int vec) {
+  const int zslices = (C + slice - 1) / slice;
+  const int lanes = std::min<int64_t>(C, slice) / vec;
+  const int rows_per_iter = std::max(256 / lanes, 1);
+  const int64_t blocks =
+      reduce ? nhwc_reduce_blocks(M, rows_per_iter, zslices * parts)
+             : nhwc_elem_blocks(M, rows_per_iter, zslices * parts);
+  return dim3(blocks, parts, zslices);
+}
+inline dim3 whiten_grid(bool reduce, int G, int64_t C, int64_t M, int64_t parts) {
+  return nhwc_grid(reduce, C, M, parts, 256, G);
+}
+inline dim3 bn_grid(bool reduce, int64_t C, int64_t M, int64_t parts) {
+  return nhwc_grid(reduce, C, M, parts, 1024, dwt::BnLanes::VC);
+}
+constexpr bool kReduce = true, kElem = false;
+
+// null for an operand the kernels treat as optional (gamma / beta without an
+// affine, the join's second consumer)
+template <typename T>
+inline T* opt_ptr(const Tensor& t, bool present) {
+  return present ? t.data_ptr<T>() : nullptr;
+}
+template <typename T>
+inline T* opt_ptr(const c10::optional<Tensor>& t) {
+  return t.has_value() ? t->data_ptr<T>() : nullptr;
+}
+
 // parts = domain branches batched into one launch (grid.y); x is the full
 // (parts*B, H, W, C) NHWC storage, M = per-part positions; acc/mean/cov are
 // stacked [parts, ...].
 void whiten_stats_partial_cl(Tensor x, Tensor acc, int64_t g, int64_t C,
                              int64_t M, int64_t parts) {
-  const int zslices = (C + 255) / 256;
   DISPATCH_FT(x, "whiten_stats_cl", [&] {
     DWT_SWITCH_G(g, {
-      const int GW = (C < 256 ? C : 256) / G;
-      dim3 grid(nhwc_reduce_blocks(M, 256 / GW, zslices * parts), parts,
-                zslices);
-      hipLaunchKernelGGL((dwt::whiten_stats_nhwc_kernel<scalar_t, G>), grid,
-                         dim3(256), 0, cur_stream(), x.data_ptr<scalar_t>(),
+      hipLaunchKernelGGL((dwt::whiten_stats_nhwc_kernel<scalar_t, G>),
+                         whiten_grid(kReduce, G, C, M, parts), dim3(256), 0,
+                         cur_stream(), x.data_ptr<scalar_t>(),
                          acc.data_ptr<float>(), (int)C, M);
     });
   });
@@ -2557,29 +2407,57 @@ void whiten_stats_cl(Tensor x, Tensor acc, Tensor mean, Tensor cov, int64_t g,
   whiten_stats_final(acc, mean, cov, g, parts * C / g, M);
 }
 
-inline int64_t nhwc_elem_blocks(int64_t M, int rows_per_iter, int zslices) {
-  const int64_t want = (M + rows_per_iter - 1) / rows_per_iter;
-  const int64_t cap = std::max<int64_t>(1, 8192 / std::max(zslices, 1));
-  return std::min(std::max<int64_t>(want, 1), cap);
+// ---- residual join fused into the last norm site (see the kernels) ----
+// res / gb are optional: without res the apply is the plain one (the RES=false
+// instantiation, which *_apply_cl launches too); without gb the join has a
+// single consumer.
+
+void whiten_apply_res_cl(Tensor x, Tensor mean, Tensor W, Tensor gamma,
+                         Tensor beta, c10::optional<Tensor> res, Tensor out,
+                         int64_t g, int64_t C, int64_t M, bool relu,
+                         bool has_affine, int64_t parts) {
+  TORCH_CHECK(!res.has_value() || (res->scalar_type() == x.scalar_type() &&
+                                   res->numel() == x.numel()),
+              "whiten_apply_res_cl: res mismatch");
+  DISPATCH_FT(x, "whiten_apply_cl", [&] {
+    DWT_SWITCH_G(g, {
+      auto launch = [&](auto with_res) {
+        constexpr bool RES = decltype(with_res)::value;
+        hipLaunchKernelGGL((dwt::whiten_apply_nhwc_kernel<scalar_t, G, RES>),
+                           whiten_grid(kElem, G, C, M, parts), dim3(256), 0,
+                           cur_stream(), x.data_ptr<scalar_t>(),
+                           opt_ptr<scalar_t>(res), mean.data_ptr<float>(),
+                           W.data_ptr<float>(),
+                           opt_ptr<scalar_t>(gamma, has_affine),
+                           opt_ptr<scalar_t>(beta, has_affine),
+                           out.data_ptr<scalar_t>(), (int)C, M, relu ? 1 : 0,
+                           has_affine ? 1 : 0);
+      };
+      if (res.has_value()) launch(std::true_type{});
+      else launch(std::false_type{});
+    });
+  });
 }
 
 void whiten_apply_cl(Tensor x, Tensor mean, Tensor W, Tensor gamma, Tensor beta,
                      Tensor out, int64_t g, int64_t C, int64_t M, bool relu,
                      bool has_affine, int64_t parts) {
-  const int zslices = (C + 255) / 256;
-  DISPATCH_FT(x, "whiten_apply_cl", [&] {
-    DWT_SWITCH_G(g, {
-      const int GW = (C < 256 ? C : 256) / G;
-      dim3 grid(nhwc_elem_blocks(M, 256 / GW, zslices * parts), parts, zslices);
-      hipLaunchKernelGGL((dwt::whiten_apply_nhwc_kernel<scalar_t, G>), grid,
-                         dim3(256), 0, cur_stream(), x.data_ptr<scalar_t>(),
-                         mean.data_ptr<float>(), W.data_ptr<float>(),
-                         has_affine ? gamma.data_ptr<scalar_t>() : nullptr,
-                         has_affine ? beta.data_ptr<scalar_t>() : nullptr,
-                         out.data_ptr<scalar_t>(), (int)C, M, relu ? 1 : 0,
-                         has_affine ? 1 : 0);
-    });
-  });
+  whiten_apply_res_cl(x, mean, W, gamma, beta, c10::nullopt, out, g, C, M, relu,
+                      has_affine, parts);
+}
+
+inline void check_join_args(const char* name, const Tensor& x, const Tensor& y,
+                            const Tensor& ga, const c10::optional<Tensor>& gb,
+                            const Tensor& gid, int64_t numel) {
+  auto all = [&](auto pred) {
+    return pred(x) && pred(y) && pred(ga) && pred(gid) &&
+           (!gb.has_value() || pred(*gb));
+  };
+  TORCH_CHECK(all([&](const Tensor& t) { return t.numel() == numel; }), name,
+              ": size mismatch");
+  TORCH_CHECK(all([&](const Tensor& t) {
+                return t.scalar_type() == x.scalar_type();
+              }), name, ": dtype mismatch");
 }
 
 void whiten_bwd_reduce_cl(Tensor x, Tensor dout, Tensor mean,
@@ -2587,21 +2465,39 @@ void whiten_bwd_reduce_cl(Tensor x, Tensor dout, Tensor mean,
                           Tensor dWacc, Tensor dgb,
                           int64_t g, int64_t C, int64_t M, bool relu,
                           bool has_affine, int64_t parts) {
-  const int zslices = (C + 255) / 256;
   DISPATCH_FT(x, "whiten_bwd_reduce_cl", [&] {
     DWT_SWITCH_G(g, {
-      const int GW = (C < 256 ? C : 256) / G;
-      dim3 grid(nhwc_reduce_blocks(M, 256 / GW, zslices * parts), parts,
-                zslices);
-      hipLaunchKernelGGL((dwt::whiten_bwd_reduce_nhwc_kernel<scalar_t, G>),
-                         grid, dim3(256), 0, cur_stream(),
-                         x.data_ptr<scalar_t>(), dout.data_ptr<scalar_t>(),
-                         mean.data_ptr<float>(),
-                         W.data_ptr<float>(),
-                         has_affine ? gamma.data_ptr<scalar_t>() : nullptr,
-                         has_affine ? beta.data_ptr<scalar_t>() : nullptr,
-                         dWacc.data_ptr<float>(), dgb.data_ptr<float>(), (int)C,
-                         M, relu ? 1 : 0, has_affine ? 1 : 0);
+      hipLaunchKernelGGL(
+          (dwt::whiten_bwd_reduce_nhwc_kernel<scalar_t, G, false>),
+          whiten_grid(kReduce, G, C, M, parts), dim3(256), 0, cur_stream(),
+          x.data_ptr<scalar_t>(), dout.data_ptr<scalar_t>(),
+          (const scalar_t*)nullptr, (const scalar_t*)nullptr,
+          (scalar_t*)nullptr, mean.data_ptr<float>(), W.data_ptr<float>(),
+          opt_ptr<scalar_t>(gamma, has_affine),
+          opt_ptr<scalar_t>(beta, has_affine), dWacc.data_ptr<float>(),
+          dgb.data_ptr<float>(), (int)C, M, relu ? 1 : 0, has_affine ? 1 : 0);
+    });
+  });
+}
+
+void whiten_join_bwd_reduce_cl(Tensor x, Tensor y, Tensor ga,
+                               c10::optional<Tensor> gb, Tensor mean, Tensor W,
+                               Tensor gamma, Tensor gid, Tensor dWacc,
+                               Tensor dgb, int64_t g, int64_t C, int64_t M,
+                               bool has_affine, int64_t parts) {
+  check_join_args("whiten_join_bwd_reduce_cl", x, y, ga, gb, gid,
+                  parts * M * C);
+  DISPATCH_FT(x, "whiten_join_bwd_reduce_cl", [&] {
+    DWT_SWITCH_G(g, {
+      hipLaunchKernelGGL(
+          (dwt::whiten_bwd_reduce_nhwc_kernel<scalar_t, G, true>),
+          whiten_grid(kReduce, G, C, M, parts), dim3(256), 0, cur_stream(),
+          x.data_ptr<scalar_t>(), ga.data_ptr<scalar_t>(),
+          y.data_ptr<scalar_t>(), opt_ptr<scalar_t>(gb),
+          gid.data_ptr<scalar_t>(), mean.data_ptr<float>(),
+          W.data_ptr<float>(), opt_ptr<scalar_t>(gamma, has_affine),
+          (const scalar_t*)nullptr, dWacc.data_ptr<float>(),
+          dgb.data_ptr<float>(), (int)C, M, 0, has_affine ? 1 : 0);
     });
   });
 }
@@ -2611,18 +2507,15 @@ void whiten_bwd_apply_cl(Tensor x, Tensor dout, Tensor mean,
                          Tensor S, Tensor corr,
                          Tensor dx, int64_t g, int64_t C, int64_t M, bool relu,
                          bool has_affine, bool train_stats, int64_t parts) {
-  const int zslices = (C + 255) / 256;
   DISPATCH_FT(x, "whiten_bwd_apply_cl", [&] {
     DWT_SWITCH_G(g, {
-      const int GW = (C < 256 ? C : 256) / G;
-      dim3 grid(nhwc_elem_blocks(M, 256 / GW, zslices * parts), parts, zslices);
       hipLaunchKernelGGL((dwt::whiten_bwd_apply_nhwc_kernel<scalar_t, G>),
-                         grid, dim3(256), 0, cur_stream(),
-                         x.data_ptr<scalar_t>(),
+                         whiten_grid(kElem, G, C, M, parts), dim3(256), 0,
+                         cur_stream(), x.data_ptr<scalar_t>(),
                          dout.data_ptr<scalar_t>(),
                          mean.data_ptr<float>(), W.data_ptr<float>(),
-                         has_affine ? gamma.data_ptr<scalar_t>() : nullptr,
-                         has_affine ? beta.data_ptr<scalar_t>() : nullptr,
+                         opt_ptr<scalar_t>(gamma, has_affine),
+                         opt_ptr<scalar_t>(beta, has_affine),
                          S.data_ptr<float>(), corr.data_ptr<float>(),
                          dx.data_ptr<scalar_t>(), (int)C, M, relu ? 1 : 0,
                          has_affine ? 1 : 0, train_stats ? 1 : 0);
@@ -2632,13 +2525,10 @@ void whiten_bwd_apply_cl(Tensor x, Tensor dout, Tensor mean,
 
 void bn_stats_partial_cl(Tensor x, Tensor acc, int64_t C, int64_t M,
                          int64_t parts) {
-  const int zslices = (C + 1023) / 1024;
   DISPATCH_FT(x, "bn_stats_cl", [&] {
-    const int NCH = (C < 1024 ? C : 1024) / 4;
-    dim3 grid(nhwc_reduce_blocks(M, 256 / NCH > 0 ? 256 / NCH : 1,
-                                 zslices * parts), parts, zslices);
-    hipLaunchKernelGGL((dwt::bn_stats_nhwc_kernel<scalar_t>), grid, dim3(256),
-                       0, cur_stream(), x.data_ptr<scalar_t>(),
+    hipLaunchKernelGGL((dwt::bn_stats_nhwc_kernel<scalar_t>),
+                       bn_grid(kReduce, C, M, parts), dim3(256), 0,
+                       cur_stream(), x.data_ptr<scalar_t>(),
                        acc.data_ptr<float>(), (int)C, M);
   });
 }
@@ -2660,41 +2550,69 @@ void bn_stats_cl(Tensor x, Tensor acc, Tensor mean, Tensor istd, Tensor var_unb,
   bn_stats_final(acc, mean, istd, var_unb, C, parts, M, eps);
 }
 
+void bn_apply_res_cl(Tensor x, Tensor mean, Tensor istd, Tensor gamma,
+                     Tensor beta, c10::optional<Tensor> res, Tensor out,
+                     int64_t C, int64_t M, bool relu, bool has_affine,
+                     int64_t parts) {
+  TORCH_CHECK(!res.has_value() || (res->scalar_type() == x.scalar_type() &&
+                                   res->numel() == x.numel()),
+              "bn_apply_res_cl: res mismatch");
+  DISPATCH_FT(x, "bn_apply_cl", [&] {
+    auto launch = [&](auto with_res) {
+      constexpr bool RES = decltype(with_res)::value;
+      hipLaunchKernelGGL((dwt::bn_apply_nhwc_kernel<scalar_t, RES>),
+                         bn_grid(kElem, C, M, parts), dim3(256), 0,
+                         cur_stream(), x.data_ptr<scalar_t>(),
+                         opt_ptr<scalar_t>(res), mean.data_ptr<float>(),
+                         istd.data_ptr<float>(),
+                         opt_ptr<scalar_t>(gamma, has_affine),
+                         opt_ptr<scalar_t>(beta, has_affine),
+                         out.data_ptr<scalar_t>(), (int)C, M, relu ? 1 : 0,
+                           has_affine ? 1 : 0);
+    };
+    if (res.has_value()) launch(std::true_type{});
+    else launch(std::false_type{});
+  });
+}
+
 void bn_apply_cl(Tensor x, Tensor mean, Tensor istd, Tensor gamma, Tensor beta,
                  Tensor out, int64_t C, int64_t M, bool relu, bool has_affine,
                  int64_t parts) {
-  const int zslices = (C + 1023) / 1024;
-  DISPATCH_FT(x, "bn_apply_cl", [&] {
-    const int NCH = (C < 1024 ? C : 1024) / 4;
-    const int rpi = std::max(256 / NCH, 1);
-    dim3 grid(nhwc_elem_blocks(M, rpi, zslices * parts), parts, zslices);
-    hipLaunchKernelGGL((dwt::bn_apply_nhwc_kernel<scalar_t>), grid,
-                       dim3(256), 0, cur_stream(), x.data_ptr<scalar_t>(),
-                       mean.data_ptr<float>(), istd.data_ptr<float>(),
-                       has_affine ? gamma.data_ptr<scalar_t>() : nullptr,
-                       has_affine ? beta.data_ptr<scalar_t>() : nullptr,
-                       out.data_ptr<scalar_t>(), (int)C, M, relu ? 1 : 0,
-                       has_affine ? 1 : 0);
-  });
+  bn_apply_res_cl(x, mean, istd, gamma, beta, c10::nullopt, out, C, M, relu,
+                  has_affine, parts);
 }
 
 void bn_bwd_reduce_cl(Tensor x, Tensor dout, Tensor mean,
                       Tensor istd, Tensor gamma, Tensor beta,
                       Tensor sums, int64_t C, int64_t M,
                       bool relu, bool has_affine, int64_t parts) {
-  const int zslices = (C + 1023) / 1024;
   DISPATCH_FT(x, "bn_bwd_reduce_cl", [&] {
-    const int NCH = (C < 1024 ? C : 1024) / 4;
-    dim3 grid(nhwc_reduce_blocks(M, 256 / NCH > 0 ? 256 / NCH : 1,
-                                 zslices * parts), parts, zslices);
-    hipLaunchKernelGGL((dwt::bn_bwd_reduce_nhwc_kernel<scalar_t>), grid,
-                       dim3(256), 0, cur_stream(), x.data_ptr<scalar_t>(),
-                       dout.data_ptr<scalar_t>(),
-                       mean.data_ptr<float>(), istd.data_ptr<float>(),
-                       has_affine ? gamma.data_ptr<scalar_t>() : nullptr,
-                       has_affine ? beta.data_ptr<scalar_t>() : nullptr,
-                       sums.data_ptr<float>(), (int)C, M, relu ? 1 : 0,
-                       has_affine ? 1 : 0);
+    hipLaunchKernelGGL(
+        (dwt::bn_bwd_reduce_nhwc_kernel<scalar_t, false>),
+        bn_grid(kReduce, C, M, parts), dim3(256), 0, cur_stream(),
+        x.data_ptr<scalar_t>(), dout.data_ptr<scalar_t>(),
+        (const scalar_t*)nullptr, (const scalar_t*)nullptr, (scalar_t*)nullptr,
+        mean.data_ptr<float>(), istd.data_ptr<float>(),
+        opt_ptr<scalar_t>(gamma, has_affine),
+        opt_ptr<scalar_t>(beta, has_affine), sums.data_ptr<float>(), (int)C, M,
+        relu ? 1 : 0, has_affine ? 1 : 0);
+  });
+}
+
+void bn_join_bwd_reduce_cl(Tensor x, Tensor y, Tensor ga,
+                           c10::optional<Tensor> gb, Tensor mean, Tensor istd,
+                           Tensor gid, Tensor sums, int64_t C, int64_t M,
+                           int64_t parts) {
+  check_join_args("bn_join_bwd_reduce_cl", x, y, ga, gb, gid, parts * M * C);
+  DISPATCH_FT(x, "bn_join_bwd_reduce_cl", [&] {
+    hipLaunchKernelGGL(
+        (dwt::bn_bwd_reduce_nhwc_kernel<scalar_t, true>),
+        bn_grid(kReduce, C, M, parts), dim3(256), 0, cur_stream(),
+        x.data_ptr<scalar_t>(), ga.data_ptr<scalar_t>(),
+        y.data_ptr<scalar_t>(), opt_ptr<scalar_t>(gb), gid.data_ptr<scalar_t>(),
+        mean.data_ptr<float>(), istd.data_ptr<float>(),
+        (const scalar_t*)nullptr, (const scalar_t*)nullptr,
+        sums.data_ptr<float>(), (int)C, M, 0, 0);
   });
 }
 
@@ -2703,149 +2621,16 @@ void bn_bwd_apply_cl(Tensor x, Tensor dout, Tensor mean,
                      Tensor sums, Tensor dx,
                      int64_t C, int64_t M, bool relu, bool has_affine,
                      bool use_batch, int64_t parts, int64_t count) {
-  const int zslices = (C + 1023) / 1024;
   DISPATCH_FT(x, "bn_bwd_apply_cl", [&] {
-    const int NCH = (C < 1024 ? C : 1024) / 4;
-    const int rpi = std::max(256 / NCH, 1);
-    dim3 grid(nhwc_elem_blocks(M, rpi, zslices * parts), parts, zslices);
-    hipLaunchKernelGGL((dwt::bn_bwd_apply_nhwc_kernel<scalar_t>), grid,
-                       dim3(256), 0, cur_stream(), x.data_ptr<scalar_t>(),
-                       dout.data_ptr<scalar_t>(),
+    hipLaunchKernelGGL((dwt::bn_bwd_apply_nhwc_kernel<scalar_t>),
+                       bn_grid(kElem, C, M, parts), dim3(256), 0, cur_stream(),
+                       x.data_ptr<scalar_t>(), dout.data_ptr<scalar_t>(),
                        mean.data_ptr<float>(), istd.data_ptr<float>(),
-                       has_affine ? gamma.data_ptr<scalar_t>() : nullptr,
-                       has_affine ? beta.data_ptr<scalar_t>() : nullptr,
+                       opt_ptr<scalar_t>(gamma, has_affine),
+                       opt_ptr<scalar_t>(beta, has_affine),
                        sums.data_ptr<float>(), dx.data_ptr<scalar_t>(), (int)C,
                        M, 1.0f / (float)count, relu ? 1 : 0,
                        has_affine ? 1 : 0, use_batch ? 1 : 0);
-  });
-}
-
-// ---- residual join fused into the last norm site (see the kernels) ----
-// res / gb are optional: without res the plain apply kernel runs (bit-
-// identical to *_apply_cl); without gb the join has a single consumer.
-// Group sizes 2 and 4 only — the NHWC route never takes g=8 (it spills).
-
-#define DWT_SWITCH_G24(g, body)                                                \
-  switch (g) {                                                                 \
-    case 2: { constexpr int G = 2; body; break; }                              \
-    case 4: { constexpr int G = 4; body; break; }                              \
-    default: TORCH_CHECK(false, "join kernels: unsupported group size ", g);   \
-  }
-
-void whiten_apply_res_cl(Tensor x, Tensor mean, Tensor W, Tensor gamma,
-                         Tensor beta, c10::optional<Tensor> res, Tensor out,
-                         int64_t g, int64_t C, int64_t M, bool relu,
-                         bool has_affine, int64_t parts) {
-  if (!res.has_value()) {
-    whiten_apply_cl(x, mean, W, gamma, beta, out, g, C, M, relu, has_affine,
-                    parts);
-    return;
-  }
-  TORCH_CHECK(res->scalar_type() == x.scalar_type() &&
-              res->numel() == x.numel(), "whiten_apply_res_cl: res mismatch");
-  const int zslices = (C + 255) / 256;
-  DISPATCH_FT(x, "whiten_apply_res_cl", [&] {
-    DWT_SWITCH_G24(g, {
-      const int GW = (C < 256 ? C : 256) / G;
-      dim3 grid(nhwc_elem_blocks(M, 256 / GW, zslices * parts), parts, zslices);
-      hipLaunchKernelGGL((dwt::whiten_apply_res_nhwc_kernel<scalar_t, G>), grid,
-                         dim3(256), 0, cur_stream(), x.data_ptr<scalar_t>(),
-                         res->data_ptr<scalar_t>(),
-                         mean.data_ptr<float>(), W.data_ptr<float>(),
-                         has_affine ? gamma.data_ptr<scalar_t>() : nullptr,
-                         has_affine ? beta.data_ptr<scalar_t>() : nullptr,
-                         out.data_ptr<scalar_t>(), (int)C, M, relu ? 1 : 0,
-                         has_affine ? 1 : 0);
-    });
-  });
-}
-
-void bn_apply_res_cl(Tensor x, Tensor mean, Tensor istd, Tensor gamma,
-                     Tensor beta, c10::optional<Tensor> res, Tensor out,
-                     int64_t C, int64_t M, bool relu, bool has_affine,
-                     int64_t parts) {
-  if (!res.has_value()) {
-    bn_apply_cl(x, mean, istd, gamma, beta, out, C, M, relu, has_affine, parts);
-    return;
-  }
-  TORCH_CHECK(res->scalar_type() == x.scalar_type() &&
-              res->numel() == x.numel(), "bn_apply_res_cl: res mismatch");
-  const int zslices = (C + 1023) / 1024;
-  DISPATCH_FT(x, "bn_apply_res_cl", [&] {
-    const int NCH = (C < 1024 ? C : 1024) / 4;
-    const int rpi = std::max(256 / NCH, 1);
-    dim3 grid(nhwc_elem_blocks(M, rpi, zslices * parts), parts, zslices);
-    hipLaunchKernelGGL((dwt::bn_apply_res_nhwc_kernel<scalar_t>), grid,
-                       dim3(256), 0, cur_stream(), x.data_ptr<scalar_t>(),
-                       res->data_ptr<scalar_t>(),
-                       mean.data_ptr<float>(), istd.data_ptr<float>(),
-                       has_affine ? gamma.data_ptr<scalar_t>() : nullptr,
-                       has_affine ? beta.data_ptr<scalar_t>() : nullptr,
-                       out.data_ptr<scalar_t>(), (int)C, M, relu ? 1 : 0,
-                       has_affine ? 1 : 0);
-  });
-}
-
-void whiten_join_bwd_reduce_cl(Tensor x, Tensor y, Tensor ga,
-                               c10::optional<Tensor> gb, Tensor mean, Tensor W,
-                               Tensor gamma, Tensor gid, Tensor dWacc,
-                               Tensor dgb, int64_t g, int64_t C, int64_t M,
-                               bool has_affine, int64_t parts) {
-  const int64_t numel = parts * M * C;
-  TORCH_CHECK(x.numel() == numel && y.numel() == numel &&
-              ga.numel() == numel && gid.numel() == numel &&
-              (!gb.has_value() || gb->numel() == numel),
-              "whiten_join_bwd_reduce_cl: size mismatch");
-  TORCH_CHECK(y.scalar_type() == x.scalar_type() &&
-              ga.scalar_type() == x.scalar_type() &&
-              gid.scalar_type() == x.scalar_type() &&
-              (!gb.has_value() || gb->scalar_type() == x.scalar_type()),
-              "whiten_join_bwd_reduce_cl: dtype mismatch");
-  const int zslices = (C + 255) / 256;
-  DISPATCH_FT(x, "whiten_join_bwd_reduce_cl", [&] {
-    DWT_SWITCH_G24(g, {
-      const int GW = (C < 256 ? C : 256) / G;
-      dim3 grid(nhwc_reduce_blocks(M, 256 / GW, zslices * parts), parts,
-                zslices);
-      hipLaunchKernelGGL((dwt::whiten_join_bwd_reduce_nhwc_kernel<scalar_t, G>),
-                         grid, dim3(256), 0, cur_stream(),
-                         x.data_ptr<scalar_t>(), y.data_ptr<scalar_t>(),
-                         ga.data_ptr<scalar_t>(),
-                         gb.has_value() ? gb->data_ptr<scalar_t>() : nullptr,
-                         mean.data_ptr<float>(), W.data_ptr<float>(),
-                         has_affine ? gamma.data_ptr<scalar_t>() : nullptr,
-                         gid.data_ptr<scalar_t>(), dWacc.data_ptr<float>(),
-                         dgb.data_ptr<float>(), (int)C, M, has_affine ? 1 : 0);
-    });
-  });
-}
-
-void bn_join_bwd_reduce_cl(Tensor x, Tensor y, Tensor ga,
-                           c10::optional<Tensor> gb, Tensor mean, Tensor istd,
-                           Tensor gid, Tensor sums, int64_t C, int64_t M,
-                           int64_t parts) {
-  const int64_t numel = parts * M * C;
-  TORCH_CHECK(x.numel() == numel && y.numel() == numel &&
-              ga.numel() == numel && gid.numel() == numel &&
-              (!gb.has_value() || gb->numel() == numel),
-              "bn_join_bwd_reduce_cl: size mismatch");
-  TORCH_CHECK(y.scalar_type() == x.scalar_type() &&
-              ga.scalar_type() == x.scalar_type() &&
-              gid.scalar_type() == x.scalar_type() &&
-              (!gb.has_value() || gb->scalar_type() == x.scalar_type()),
-              "bn_join_bwd_reduce_cl: dtype mismatch");
-  const int zslices = (C + 1023) / 1024;
-  DISPATCH_FT(x, "bn_join_bwd_reduce_cl", [&] {
-    const int NCH = (C < 1024 ? C : 1024) / 4;
-    dim3 grid(nhwc_reduce_blocks(M, 256 / NCH > 0 ? 256 / NCH : 1,
-                                 zslices * parts), parts, zslices);
-    hipLaunchKernelGGL((dwt::bn_join_bwd_reduce_nhwc_kernel<scalar_t>), grid,
-                       dim3(256), 0, cur_stream(), x.data_ptr<scalar_t>(),
-                       y.data_ptr<scalar_t>(), ga.data_ptr<scalar_t>(),
-                       gb.has_value() ? gb->data_ptr<scalar_t>() : nullptr,
-                       mean.data_ptr<float>(), istd.data_ptr<float>(),
-                       gid.data_ptr<scalar_t>(), sums.data_ptr<float>(), (int)C,
-                       M);
   });
 }
 

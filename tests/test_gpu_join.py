@@ -16,9 +16,15 @@ PARTS = 3
 # 512 = two 256-channel chunks; (512, 1, 2, 2) has M = g positions per branch
 # and runs on scaled inputs (see _scales), (512, 2, 2, 2) is the same
 # two-chunk case with M > g at unit scale.
+#
+# Whitening (g=2), the other group size the NHWC kernels are routed for:
+# (64, 2, 3, 3) has 32 group lanes, so 8 rows per iteration, and M = 18 is no
+# multiple of that; (512, 2, 2, 2) is two 256-channel chunks with 128 group
+# lanes, 2 rows per iteration, M = 8.  Both have M > g, so unit scale.
 BN_SHAPES = [(64, 2, 3, 3), (256, 2, 2, 2), (2048, 1, 2, 2)]
 WH_SHAPES = [(64, 2, 3, 3), (256, 2, 3, 3), (512, 1, 2, 2), (512, 2, 2, 2)]
-G = 4
+WH_G2_SHAPES = [(64, 2, 3, 3), (512, 2, 2, 2)]
+G = 4  # group size wherever a test does not parametrise it
 CASES = ["both", "a_only", "b_only"]
 
 
@@ -30,15 +36,15 @@ def dev():
     return torch.device("cuda:0")
 
 
-def _cfg(kind, c, training=True):
+def _cfg(kind, c, training=True, g=G):
     if kind == "bn":
         return dict(parts=PARTS if training else 1, eps=1e-5, momentum=0.1,
                     training=training, relu=False)
-    return dict(parts=PARTS if training else 1, num_groups=c // G, eps=1e-3,
+    return dict(parts=PARTS if training else 1, num_groups=c // g, eps=1e-3,
                 momentum=0.1, training=training, mode="chol", relu=False)
 
 
-def _buffers(kind, c, dev, parts, seed=None):
+def _buffers(kind, c, dev, parts, seed=None, g=G):
     """Running-stat buffers; with a seed, non-trivial ones for eval mode."""
     if kind == "bn":
         rms = [torch.zeros(c, device=dev) for _ in range(parts)]
@@ -48,9 +54,9 @@ def _buffers(kind, c, dev, parts, seed=None):
             rms = [torch.randn(c, generator=gen).to(dev) * 0.3 for _ in rms]
             rvs = [(torch.rand(c, generator=gen) + 0.5).to(dev) for _ in rvs]
         return rms, rvs
-    ng = c // G
+    ng = c // g
     rms = [torch.zeros(1, c, 1, 1, device=dev) for _ in range(parts)]
-    rvs = [torch.eye(G, device=dev).repeat(ng, 1, 1).contiguous()
+    rvs = [torch.eye(g, device=dev).repeat(ng, 1, 1).contiguous()
            for _ in range(parts)]
     if seed is not None:
         gen = torch.Generator(device="cpu").manual_seed(seed)
@@ -58,13 +64,13 @@ def _buffers(kind, c, dev, parts, seed=None):
                for _ in rms]
         new = []
         for _ in rvs:
-            a = torch.randn(ng, G, G, generator=gen) * 0.3
-            new.append((a @ a.transpose(1, 2) + torch.eye(G)).to(dev))
+            a = torch.randn(ng, g, g, generator=gen) * 0.3
+            new.append((a @ a.transpose(1, 2) + torch.eye(g)).to(dev))
         rvs = new
     return rms, rvs
 
 
-def _scales(kind, shape):
+def _scales(kind, shape, g=G):
     """(scale of the random x, scale of the consumers' loss weights).
 
     A whitening branch with M = b*h*w <= g
@@ -82,7 +88,7 @@ def _scales(kind, shape):
     shrink with the loss weights, so their fp32 tolerances are scaled by the
     same factor for this shape (_tols)."""
     c, b, h, w = shape
-    if kind == "wh" and b * h * w <= G:
+    if kind == "wh" and b * h * w <= g:
         return 0.1, 1e-3 ** 0.5
     return 1.0, 1.0
 
@@ -154,32 +160,34 @@ def _shapes(kind):
     return BN_SHAPES if kind == "bn" else WH_SHAPES
 
 
-ALL = [(k, s) for k in ("bn", "wh") for s in _shapes(k)]
-IDS = [f"{k}-C{s[0]}b{s[1]}" for k, s in ALL]
+ALL = [(k, s, G) for k in ("bn", "wh") for s in _shapes(k)] \
+    + [("wh", s, 2) for s in WH_G2_SHAPES]
+IDS = [f"{k}-C{s[0]}b{s[1]}" if g == G else f"{k}-g{g}-C{s[0]}b{s[1]}"
+       for k, s, g in ALL]
 
 
-def _tols(kind, shape):
+def _tols(kind, shape, g=G):
     """fp32 (out, dx, d_identity, dgamma/dbeta) tolerances: those of
     test_bn_channels_last_parity / test_whiten_channels_last_parity, the
     last two scaled down with the loss weights where _scales shrinks them."""
     t_out, t_dx, t_p = (1e-4, 1e-3, 1e-2) if kind == "bn" else (3e-4, 2e-3, 3e-2)
-    g_scale = _scales(kind, shape)[1]
+    g_scale = _scales(kind, shape, g)[1]
     return t_out, t_dx, t_dx * g_scale, t_p * g_scale
 
 
 @pytest.mark.parametrize("case", CASES)
-@pytest.mark.parametrize("kind,shape", ALL, ids=IDS)
-def test_join_parity_fp32(dev, kind, shape, case):
+@pytest.mark.parametrize("kind,shape,g", ALL, ids=IDS)
+def test_join_parity_fp32(dev, kind, shape, g, case):
     c = shape[0]
     inp = _inputs(*shape, dev, torch.float32, seed=20 + c,
-                  scales=_scales(kind, shape))
-    cfg = _cfg(kind, c)
-    bufs_f = _buffers(kind, c, dev, PARTS)
-    bufs_t = _buffers(kind, c, dev, PARTS)
+                  scales=_scales(kind, shape, g))
+    cfg = _cfg(kind, c, g=g)
+    bufs_f = _buffers(kind, c, dev, PARTS, g=g)
+    bufs_t = _buffers(kind, c, dev, PARTS, g=g)
     y_f, dx_f, did_f, dg_f, db_f = _run(kind, "fused", inp, cfg, bufs_f, case)
     y_t, dx_t, did_t, dg_t, db_t = _run(kind, "torch", inp, cfg, bufs_t, case)
-    t_out, t_dx, t_did, t_p = _tols(kind, shape)
-    print(f"{kind} {shape} {case}: y {_maxerr(y_f, y_t):.3g} "
+    t_out, t_dx, t_did, t_p = _tols(kind, shape, g)
+    print(f"{kind} g={g} {shape} {case}: y {_maxerr(y_f, y_t):.3g} "
           f"dx {_maxerr(dx_f, dx_t):.3g} did {_maxerr(did_f, did_t):.3g} "
           f"dgamma {_maxerr(dg_f, dg_t):.3g} dbeta {_maxerr(db_f, db_t):.3g}")
     assert torch.allclose(y_f, y_t, atol=t_out), _maxerr(y_f, y_t)
@@ -192,18 +200,18 @@ def test_join_parity_fp32(dev, kind, shape, case):
 
 
 @pytest.mark.parametrize("case", CASES)
-@pytest.mark.parametrize("kind,shape", ALL, ids=IDS)
-def test_join_bf16_no_worse_than_unfused(dev, kind, shape, case):
+@pytest.mark.parametrize("kind,shape,g", ALL, ids=IDS)
+def test_join_bf16_no_worse_than_unfused(dev, kind, shape, g, case):
     """fp32 reference on the same (bf16-representable) inputs; the fused bf16
     path may err at most 1.5x what the unfused bf16 HIP path errs — it rounds
     once in the forward instead of twice; 1.5x covers atomic-order noise."""
     c = shape[0]
     inp = _inputs(*shape, dev, torch.bfloat16, seed=40 + c,
-                  scales=_scales(kind, shape))
-    cfg = _cfg(kind, c)
+                  scales=_scales(kind, shape, g))
+    cfg = _cfg(kind, c, g=g)
 
     def run(impl, dtype):
-        return _run(kind, impl, inp, cfg, _buffers(kind, c, dev, PARTS), case,
+        return _run(kind, impl, inp, cfg, _buffers(kind, c, dev, PARTS, g=g), case,
                     dtype=dtype)
 
     ref = run("torch", torch.float32)
@@ -212,7 +220,7 @@ def test_join_bf16_no_worse_than_unfused(dev, kind, shape, case):
     for name, i in (("y", 0), ("dx", 1), ("d_identity", 2)):
         e_f = _maxerr(fused[i], ref[i])
         e_u = _maxerr(unfused[i], ref[i])
-        print(f"{kind} {shape} {case} {name}: fused {e_f:.4g} unfused {e_u:.4g}")
+        print(f"{kind} g={g} {shape} {case} {name}: fused {e_f:.4g} unfused {e_u:.4g}")
         assert e_f <= 1.5 * e_u, (name, e_f, e_u)
         atol, rtol = (0.1, 0.05) if name == "y" else (0.2, 0.1)
         assert torch.allclose(fused[i].float(), ref[i], atol=atol, rtol=rtol), \

@@ -239,7 +239,9 @@ def test_lenet_gpu_step(dev):
 
 
 @pytest.mark.parametrize("mode", ["chol", "zca"])
-@pytest.mark.parametrize("c,groups_of", [(64, 16), (256, 64), (512, 128)])
+# (64, 32) is g=2: 32 group lanes, 8 rows per iteration over 120 positions
+@pytest.mark.parametrize("c,groups_of", [(64, 16), (256, 64), (512, 128),
+                                         (64, 32)])
 def test_whiten_channels_last_parity(dev, mode, c, groups_of):
     torch.manual_seed(10)
     parts = 3
