@@ -30,6 +30,9 @@ def _load():
             spec = importlib.util.spec_from_file_location("dwt_amd.kernels._dwt_hip", sos[0])
             mod = importlib.util.module_from_spec(spec)
             spec.loader.exec_module(mod)
+            # DWT_AMD_NORM_WIDE=0 forces the narrow (8-byte for bf16) forms of
+            # the NHWC norm kernels — the A/B switch of docs/KERNELS.md
+            mod.set_norm_wide(os.environ.get("DWT_AMD_NORM_WIDE", "1") != "0")
             _ext = mod
     except Exception as exc:  # pragma: no cover - build issues surface here
         warnings.warn(f"dwt_amd HIP extension failed to load: {exc}")

@@ -32,6 +32,10 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <initializer_list>
+#include <string>
+#include <type_traits>
+#include <vector>
 
 #define DEV_INLINE __device__ __forceinline__
 
@@ -1088,13 +1092,120 @@ struct WhitenLanes {
   }
 };
 
+// How a whitening lane moves its group's rows.  Narrow (WIDE = false): one
+// row per loop iteration, one G-channel access per operand — 8 bytes for
+// bf16 g=4.  Wide (bf16, g=4 only): the lanes pair up as (t, t^1), adjacent
+// group slots 2j and 2j+1 of one row block, and cover TWO rows per iteration
+// with 16-byte accesses: both address the 16-byte chunk that holds their two
+// groups, the even lane at row m, the odd lane at row m+1.  After a load the
+// two swap the half that is the other's group (a quad-permute DPP move), so
+// each holds its OWN group for both rows: the parameters (W, S, mean, ...)
+// stay one set per lane, and two rows are in flight.  Before a store they
+// swap back.  The first_row()/row_stride() of WhitenLanes then count row
+// PAIRS: rows 2*first_row(), 2*first_row() + 1, then 2*row_stride() on.
+//
+// At an odd M the last pair lacks its second row.  Both lanes stay live
+// through the swaps; the odd lane's load is zero-filled and its store
+// skipped.  A zero row adds nothing to any of the sums (the gradient operand
+// of the backward reduces is zero there, and so is every product with it).
+template <typename T, int G, bool WIDE>
+struct WhitenRows {
+  static_assert(!WIDE, "the lane-pair form is bf16 g=4 only");
+  static constexpr int NR = 1;
+  const WhitenLanes<G>& L;
+  int C; int64_t M;
+  DEV_INLINE WhitenRows(const WhitenLanes<G>& L_, int C_, int64_t M_)
+      : L(L_), C(C_), M(M_) {}
+  DEV_INLINE int64_t first() const { return L.first_row(); }
+  DEV_INLINE int64_t stride() const { return L.row_stride(); }
+  // element offset of this lane's access for the rows at m
+  DEV_INLINE int64_t off(int64_t m) const { return m * C + L.c0; }
+  DEV_INLINE void load_at(const T* p, int64_t o, int64_t, float (&v)[1][G]) const {
+    load_group<T, G>(p + o, v[0]);
+  }
+  DEV_INLINE void store_at(T* p, int64_t o, int64_t, const float (&v)[1][G]) const {
+    store_group<T, G>(p + o, v[0]);
+  }
+  DEV_INLINE void load(const T* p, int64_t m, float (&v)[1][G]) const {
+    load_group<T, G>(p + m * C + L.c0, v[0]);
+  }
+  DEV_INLINE void store(T* p, int64_t m, const float (&v)[1][G]) const {
+    store_group<T, G>(p + m * C + L.c0, v[0]);
+  }
+};
+
+// the other lane of the pair's value: quad_perm [1,0,3,2], all rows and banks
+DEV_INLINE unsigned int pair_swap(unsigned int v) {
+  return (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF,
+                                                   false);
+}
+
+template <>
+struct WhitenRows<c10::BFloat16, 4, true> {
+  using T = c10::BFloat16;
+  static constexpr int NR = 2;
+  const WhitenLanes<4>& L;
+  int C; int64_t M;
+  DEV_INLINE WhitenRows(const WhitenLanes<4>& L_, int C_, int64_t M_)
+      : L(L_), C(C_), M(M_) {}
+  DEV_INLINE int64_t first() const { return 2 * L.first_row(); }
+  DEV_INLINE int64_t stride() const { return 2 * L.row_stride(); }
+  DEV_INLINE bool odd() const { return L.slot & 1; }
+  // element offset of this lane's access: its row of the pair at m, the
+  // 8-channel chunk of its pair
+  DEV_INLINE int64_t off(int64_t m) const {
+    return (m + (L.slot & 1)) * C + (L.c0 & ~7);
+  }
+  DEV_INLINE bool has_row(int64_t m) const { return m + (L.slot & 1) < M; }
+  // v[0], v[1]: this lane's group at rows m, m+1 (zeros for a missing row)
+  DEV_INLINE void load(const T* p, int64_t m, float (&v)[2][4]) const {
+    load_at(p, off(m), m, v);
+  }
+  DEV_INLINE void store(T* p, int64_t m, const float (&v)[2][4]) const {
+    store_at(p, off(m), m, v);
+  }
+  DEV_INLINE void load_at(const T* p, int64_t at, int64_t m,
+                          float (&v)[2][4]) const {
+    uint4 q = make_uint4(0u, 0u, 0u, 0u);
+    if (has_row(m)) q = *reinterpret_cast<const uint4*>(p + at);
+    // (x, y) is group 2j, (z, w) group 2j+1: send the other lane's group
+    const bool o = odd();
+    const unsigned int r0 = pair_swap(o ? q.x : q.z);
+    const unsigned int r1 = pair_swap(o ? q.y : q.w);
+    // even: own row m is (x, y), row m+1 arrives; odd: row m arrives, own
+    // row m+1 is (z, w)
+    bf16_to_f32x2(o ? r0 : q.x, v[0]);
+    bf16_to_f32x2(o ? r1 : q.y, v[0] + 2);
+    bf16_to_f32x2(o ? q.z : r0, v[1]);
+    bf16_to_f32x2(o ? q.w : r1, v[1] + 2);
+  }
+  DEV_INLINE void store_at(T* p, int64_t at, int64_t m,
+                           const float (&v)[2][4]) const {
+    const unsigned int a0 = f32x2_to_bf16(v[0][0], v[0][1]);
+    const unsigned int a1 = f32x2_to_bf16(v[0][2], v[0][3]);
+    const unsigned int b0 = f32x2_to_bf16(v[1][0], v[1][1]);
+    const unsigned int b1 = f32x2_to_bf16(v[1][2], v[1][3]);
+    // the even lane stores row m and needs the odd lane's row m; the odd
+    // lane stores row m+1 and needs the even lane's row m+1
+    const bool o = odd();
+    const unsigned int r0 = pair_swap(o ? a0 : b0);
+    const unsigned int r1 = pair_swap(o ? a1 : b1);
+    if (has_row(m)) {
+      *reinterpret_cast<uint4*>(p + at) =
+          o ? make_uint4(r0, r1, b0, b1) : make_uint4(a0, a1, r0, r1);
+    }
+  }
+};
+
 // fused mean+cov, NHWC
-template <typename T, int G>
+template <typename T, int G, bool WIDE>
 __global__ void whiten_stats_nhwc_kernel(
     const T* __restrict__ x, float* __restrict__ acc, int C, int64_t M) {
   const int part = blockIdx.y;
   x += (int64_t)part * M * C;
   const WhitenLanes<G> L(C, part);
+  const WhitenRows<T, G, WIDE> Rw(L, C, M);
+  constexpr int NR = WhitenRows<T, G, WIDE>::NR;
 
   float s[G], p[G][G];
 #pragma unroll
@@ -1103,15 +1214,18 @@ __global__ void whiten_stats_nhwc_kernel(
 #pragma unroll
     for (int j = 0; j < G; ++j) p[i][j] = 0.f;
   }
-  const int64_t stride = L.row_stride();
-  for (int64_t m = L.first_row(); m < M; m += stride) {
-    float v[G];
-    load_group<T, G>(x + m * C + L.c0, v);
+  const int64_t stride = Rw.stride();
+  for (int64_t m = Rw.first(); m < M; m += stride) {
+    float v[NR][G];
+    Rw.load(x, m, v);
 #pragma unroll
-    for (int i = 0; i < G; ++i) {
-      s[i] += v[i];
+    for (int r = 0; r < NR; ++r) {
 #pragma unroll
-      for (int j = 0; j <= i; ++j) p[i][j] += v[i] * v[j];
+      for (int i = 0; i < G; ++i) {
+        s[i] += v[r][i];
+#pragma unroll
+        for (int j = 0; j <= i; ++j) p[i][j] += v[r][i] * v[r][j];
+      }
     }
   }
   // reduce within the wave over lanes sharing the same group (stride GW in
@@ -1155,7 +1269,7 @@ __global__ void whiten_stats_nhwc_kernel(
 // last norm site: out = relu?(norm(x) + res), the add done in fp32 and
 // rounded once on the store, so the norm output is never materialised.  res
 // is one more streamed operand, offset per branch like x (unused if !RES).
-template <typename T, int G, bool RES>
+template <typename T, int G, bool WIDE, bool RES>
 __global__ void whiten_apply_nhwc_kernel(
     const T* __restrict__ x, const T* __restrict__ res,
     const float* __restrict__ mean,
@@ -1177,24 +1291,29 @@ __global__ void whiten_apply_nhwc_kernel(
 #pragma unroll
     for (int j = 0; j < G; ++j) Wr[i][j] = W[((int64_t)L.grp * G + i) * G + j];
   }
-  const int64_t stride = L.row_stride();
-  for (int64_t m = L.first_row(); m < M; m += stride) {
-    [[maybe_unused]] float r[G];
-    float v[G], y[G];
-    load_group<T, G>(x + m * C + L.c0, v);
-    if constexpr (RES) load_group<T, G>(res + m * C + L.c0, r);
+  const WhitenRows<T, G, WIDE> Rw(L, C, M);
+  constexpr int NR = WhitenRows<T, G, WIDE>::NR;
+  const int64_t stride = Rw.stride();
+  for (int64_t m = Rw.first(); m < M; m += stride) {
+    [[maybe_unused]] float r[NR][G];
+    float v[NR][G], y[NR][G];
+    Rw.load(x, m, v);
+    if constexpr (RES) Rw.load(res, m, r);
 #pragma unroll
-    for (int j = 0; j < G; ++j) v[j] -= m_[j];
+    for (int n = 0; n < NR; ++n) {
 #pragma unroll
-    for (int i = 0; i < G; ++i) {
-      float a = 0.f;
+      for (int j = 0; j < G; ++j) v[n][j] -= m_[j];
 #pragma unroll
-      for (int j = 0; j < G; ++j) a += Wr[i][j] * v[j];
-      a = a * gm[i] + bt[i];
-      if constexpr (RES) a += r[i];
-      y[i] = relu ? fmaxf(a, 0.f) : a;
+      for (int i = 0; i < G; ++i) {
+        float a = 0.f;
+#pragma unroll
+        for (int j = 0; j < G; ++j) a += Wr[i][j] * v[n][j];
+        a = a * gm[i] + bt[i];
+        if constexpr (RES) a += r[n][i];
+        y[n][i] = relu ? fmaxf(a, 0.f) : a;
+      }
     }
-    store_group<T, G>(out + m * C + L.c0, y);
+    Rw.store(out, m, y);
   }
 }
 
@@ -1232,7 +1351,7 @@ DEV_INLINE void join_sum(const T* __restrict__ ga, const T* __restrict__ gb,
 // and address their operands in their own order (element offset shared in
 // JOIN, recomputed per operand in plain): the register allocation of the
 // bf16 instantiations follows that order, and it is kept as measured.
-template <typename T, int G, bool JOIN>
+template <typename T, int G, bool WIDE, bool JOIN>
 __global__ void whiten_bwd_reduce_nhwc_kernel(
     const T* __restrict__ x, const T* __restrict__ dout,
     const T* __restrict__ y, const T* __restrict__ gb, T* __restrict__ gid,
@@ -1269,43 +1388,61 @@ __global__ void whiten_bwd_reduce_nhwc_kernel(
 #pragma unroll
     for (int j = 0; j < G; ++j) dWl[i][j] = 0.f;
   }
-  const int64_t stride = L.row_stride();
-  for (int64_t m = L.first_row(); m < M; m += stride) {
-    float xv[G], dyv[G];
+  const WhitenRows<T, G, WIDE> Rw(L, C, M);
+  constexpr int NR = WhitenRows<T, G, WIDE>::NR;
+  const int64_t stride = Rw.stride();
+  for (int64_t m = Rw.first(); m < M; m += stride) {
+    float xv[NR][G], dyv[NR][G];
     if constexpr (JOIN) {
-      const int64_t off = m * C + L.c0;
-      float yv[G];
-      load_group<T, G>(x + off, xv);
-      load_group<T, G>(y + off, yv);
-      join_sum<T, G>(dout, gb, off, dyv);
+      const int64_t off = Rw.off(m);
+      float yv[NR][G];
+      Rw.load_at(x, off, m, xv);
+      Rw.load_at(y, off, m, yv);
+      Rw.load_at(dout, off, m, dyv);
+      if (gb) {  // two consumers: ga + gb
+        float t[NR][G];
+        Rw.load_at(gb, off, m, t);
 #pragma unroll
-      for (int j = 0; j < G; ++j) {
-        dyv[j] = yv[j] > 0.f ? round_to<T>(dyv[j]) : 0.f;
-        xv[j] -= m_[j];
+        for (int n = 0; n < NR; ++n)
+#pragma unroll
+          for (int j = 0; j < G; ++j) dyv[n][j] += t[n][j];
       }
-      store_group<T, G>(gid + off, dyv);
-    } else {
-      load_group<T, G>(x + m * C + L.c0, xv);
-      load_group<T, G>(dout + m * C + L.c0, dyv);
 #pragma unroll
-      for (int j = 0; j < G; ++j) xv[j] -= m_[j];
+      for (int n = 0; n < NR; ++n)
+#pragma unroll
+        for (int j = 0; j < G; ++j) {
+          dyv[n][j] = yv[n][j] > 0.f ? round_to<T>(dyv[n][j]) : 0.f;
+          xv[n][j] -= m_[j];
+        }
+      Rw.store_at(gid, off, m, dyv);
+    } else {
+      Rw.load(x, m, xv);
+      Rw.load(dout, m, dyv);
+#pragma unroll
+      for (int n = 0; n < NR; ++n)
+#pragma unroll
+        for (int j = 0; j < G; ++j) xv[n][j] -= m_[j];
     }
 #pragma unroll
-    for (int i = 0; i < G; ++i) {
-      float y0 = 0.f;
+    for (int n = 0; n < NR; ++n) {
 #pragma unroll
-      for (int j = 0; j < G; ++j) y0 += Wr[i][j] * xv[j];
-      float dy = dyv[i];
-      if constexpr (!JOIN) {
-        // relu mask recomputed from the same fp32 pre-activation the forward
-        // stored (bf16 rounding preserves sign) — saves the out re-read
-        if (relu && gm[i] * y0 + bt[i] <= 0.f) dy = 0.f;
+      for (int i = 0; i < G; ++i) {
+        float y0 = 0.f;
+#pragma unroll
+        for (int j = 0; j < G; ++j) y0 += Wr[i][j] * xv[n][j];
+        float dy = dyv[n][i];
+        if constexpr (!JOIN) {
+          // relu mask recomputed from the same fp32 pre-activation the
+          // forward stored (bf16 rounding preserves sign) — saves the out
+          // re-read
+          if (relu && gm[i] * y0 + bt[i] <= 0.f) dy = 0.f;
+        }
+        db[i] += dy;
+        dg[i] += dy * y0;
+        const float dy0 = dy * gm[i];
+#pragma unroll
+        for (int j = 0; j < G; ++j) dWl[i][j] += dy0 * xv[n][j];
       }
-      db[i] += dy;
-      dg[i] += dy * y0;
-      const float dy0 = dy * gm[i];
-#pragma unroll
-      for (int j = 0; j < G; ++j) dWl[i][j] += dy0 * xv[j];
     }
   }
   // per-block LDS accumulate by group slot, then one global atomic per value
@@ -1335,7 +1472,7 @@ __global__ void whiten_bwd_reduce_nhwc_kernel(
 }
 
 // backward apply, NHWC (fixed group per thread, W^T/S in registers)
-template <typename T, int G>
+template <typename T, int G, bool WIDE>
 __global__ void whiten_bwd_apply_nhwc_kernel(
     const T* __restrict__ x, const T* __restrict__ dout,
     const float* __restrict__ mean,
@@ -1364,41 +1501,64 @@ __global__ void whiten_bwd_apply_nhwc_kernel(
       Sr[i][j] = train_stats ? S[((int64_t)L.grp * G + i) * G + j] : 0.f;
     }
   }
-  const int64_t stride = L.row_stride();
-  for (int64_t m = L.first_row(); m < M; m += stride) {
-    float xv[G], dyv[G], r[G];
-    load_group<T, G>(x + m * C + L.c0, xv);
-    load_group<T, G>(dout + m * C + L.c0, dyv);
+  const WhitenRows<T, G, WIDE> Rw(L, C, M);
+  constexpr int NR = WhitenRows<T, G, WIDE>::NR;
+  const int64_t stride = Rw.stride();
+  for (int64_t m = Rw.first(); m < M; m += stride) {
+    float xv[NR][G], dyv[NR][G], r[NR][G];
+    Rw.load(x, m, xv);
+    Rw.load(dout, m, dyv);
 #pragma unroll
-    for (int j = 0; j < G; ++j) xv[j] -= m_[j];
-    if (relu) {
+    for (int n = 0; n < NR; ++n) {
+#pragma unroll
+      for (int j = 0; j < G; ++j) xv[n][j] -= m_[j];
+      if (relu) {
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+          float y0 = 0.f;
+#pragma unroll
+          for (int j = 0; j < G; ++j) y0 += Wr[i][j] * xv[n][j];
+          if (gm[i] * y0 + bt[i] <= 0.f) dyv[n][i] = 0.f;
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < G; ++j) dyv[n][j] *= gm[j];
 #pragma unroll
       for (int i = 0; i < G; ++i) {
-        float y0 = 0.f;
+        float a = -cr[i];
 #pragma unroll
-        for (int j = 0; j < G; ++j) y0 += Wr[i][j] * xv[j];
-        if (gm[i] * y0 + bt[i] <= 0.f) dyv[i] = 0.f;
+        for (int j = 0; j < G; ++j)
+          a += Wt[i][j] * dyv[n][j] + Sr[i][j] * xv[n][j];
+        r[n][i] = a;
       }
     }
-#pragma unroll
-    for (int j = 0; j < G; ++j) dyv[j] *= gm[j];
-#pragma unroll
-    for (int i = 0; i < G; ++i) {
-      float a = -cr[i];
-#pragma unroll
-      for (int j = 0; j < G; ++j) a += Wt[i][j] * dyv[j] + Sr[i][j] * xv[j];
-      r[i] = a;
-    }
-    store_group<T, G>(dx + m * C + L.c0, r);
+    Rw.store(dx, m, r);
   }
 }
 
-// Lane map of the NHWC BN kernels: per-lane VC-channel chunks.  blockIdx.y =
-// domain branch as in the whitening family (acc/sums/mean/istd stacked
-// [parts, ...]); blockIdx.z = 1024-channel slice of CW channels, in which
-// lane t owns channels c0..c0+VC-1 and rows as in WhitenLanes.
+// Calls body(m, n) over this lane's rows: while R rows remain, once per R of
+// them with n = integral_constant<int, R> (rows m, m + stride, ...: the body
+// issues all their loads before the first use), then row by row with n = 1.
+// R = 1 is the plain grid-stride loop.
+template <int R, typename Lanes, typename F>
+DEV_INLINE void for_rows(const Lanes& L, int64_t M, F&& body) {
+  const int64_t stride = L.row_stride();
+  int64_t m = L.first_row();
+  if constexpr (R > 1) {
+    for (; m + (R - 1) * stride < M; m += R * stride)
+      body(m, stride, std::integral_constant<int, R>{});
+  }
+  for (; m < M; m += stride) body(m, stride, std::integral_constant<int, 1>{});
+}
+
+// Lane map of the NHWC BN kernels: per-lane VC-channel chunks (VC = 4, or 8
+// for bf16 where the launcher finds 16-byte accesses possible: see bn_wide).
+// blockIdx.y = domain branch as in the whitening family (acc/sums/mean/istd
+// stacked [parts, ...]); blockIdx.z = 1024-channel slice of CW channels, in
+// which lane t owns channels c0..c0+VC-1 and rows as in WhitenLanes.
+template <int VC_>
 struct BnLanes {
-  static constexpr int VC = 4;
+  static constexpr int VC = VC_;
   int CW, c0, rows_per_iter, row_in_block;
   DEV_INLINE explicit BnLanes(int C) {
     CW = C < 1024 ? C : 1024;
@@ -1417,16 +1577,16 @@ struct BnLanes {
 
 // Two per-lane sums per channel into this part's acc[2][C]: per-block LDS
 // accumulation -> one global atomic per channel per block.
-DEV_INLINE void bn_two_sum_flush(const BnLanes& L, int C,
-                                 const float (&a)[BnLanes::VC],
-                                 const float (&b)[BnLanes::VC],
+template <int VC>
+DEV_INLINE void bn_two_sum_flush(const BnLanes<VC>& L, int C,
+                                 const float (&a)[VC], const float (&b)[VC],
                                  float* __restrict__ acc /* this part's */) {
   __shared__ float lacc[2 * 1024];
   const int cb = L.c0 - blockIdx.z * 1024;
   for (int k = threadIdx.x; k < 2 * L.CW; k += blockDim.x) lacc[k] = 0.f;
   __syncthreads();
 #pragma unroll
-  for (int k = 0; k < BnLanes::VC; ++k) {
+  for (int k = 0; k < VC; ++k) {
     atomicAdd(&lacc[cb + k], a[k]);
     atomicAdd(&lacc[L.CW + cb + k], b[k]);
   }
@@ -1437,44 +1597,48 @@ DEV_INLINE void bn_two_sum_flush(const BnLanes& L, int C,
   }
 }
 
-template <typename T>
+// In the BN kernels VC is the lane's chunk width and R its rows per loop
+// iteration (for_rows).
+template <typename T, int VC, int R>
 __global__ void bn_stats_nhwc_kernel(
     const T* __restrict__ x, float* __restrict__ acc, int C, int64_t M) {
-  constexpr int VC = BnLanes::VC;
   const int part = blockIdx.y;
   x += (int64_t)part * M * C;
   acc += (int64_t)part * 2 * C;
-  const BnLanes L(C);
+  const BnLanes<VC> L(C);
   float s[VC], ss[VC];
 #pragma unroll
   for (int k = 0; k < VC; ++k) { s[k] = 0.f; ss[k] = 0.f; }
-  const int64_t stride = L.row_stride();
-  for (int64_t m = L.first_row(); m < M; m += stride) {
-    float v[VC];
-    load_group<T, VC>(x + m * C + L.c0, v);
+  for_rows<R>(L, M, [&](int64_t m, int64_t stride, auto n) {
+    constexpr int N = decltype(n)::value;
+    float v[N][VC];
 #pragma unroll
-    for (int k = 0; k < VC; ++k) { s[k] += v[k]; ss[k] += v[k] * v[k]; }
-  }
+    for (int r = 0; r < N; ++r)
+      load_group<T, VC>(x + (m + r * stride) * C + L.c0, v[r]);
+#pragma unroll
+    for (int r = 0; r < N; ++r)
+#pragma unroll
+      for (int k = 0; k < VC; ++k) { s[k] += v[r][k]; ss[k] += v[r][k] * v[r][k]; }
+  });
   bn_two_sum_flush(L, C, s, ss, acc);
 }
 
 // RES: the residual join of the block's last norm site, as in
 // whiten_apply_nhwc_kernel
-template <typename T, bool RES>
+template <typename T, int VC, int R, bool RES>
 __global__ void bn_apply_nhwc_kernel(
     const T* __restrict__ x, const T* __restrict__ res,
     const float* __restrict__ mean,
     const float* __restrict__ istd, const T* __restrict__ gamma,
     const T* __restrict__ beta, T* __restrict__ out, int C, int64_t M,
     int relu, int has_affine) {
-  constexpr int VC = BnLanes::VC;
   const int part = blockIdx.y;
   x += (int64_t)part * M * C;
   if constexpr (RES) res += (int64_t)part * M * C;
   out += (int64_t)part * M * C;
   mean += (int64_t)part * C;
   istd += (int64_t)part * C;
-  const BnLanes L(C);
+  const BnLanes<VC> L(C);
   float mu[VC], is[VC], gm[VC], bt[VC];
 #pragma unroll
   for (int k = 0; k < VC; ++k) {
@@ -1483,25 +1647,31 @@ __global__ void bn_apply_nhwc_kernel(
     gm[k] = has_affine ? ldf(gamma + L.c0 + k) : 1.f;
     bt[k] = has_affine ? ldf(beta + L.c0 + k) : 0.f;
   }
-  const int64_t stride = L.row_stride();
-  for (int64_t m = L.first_row(); m < M; m += stride) {
-    [[maybe_unused]] float r[VC];
-    float v[VC];
-    load_group<T, VC>(x + m * C + L.c0, v);
-    if constexpr (RES) load_group<T, VC>(res + m * C + L.c0, r);
+  for_rows<R>(L, M, [&](int64_t m, int64_t stride, auto n) {
+    constexpr int N = decltype(n)::value;
+    [[maybe_unused]] float r[N][VC];
+    float v[N][VC];
 #pragma unroll
-    for (int k = 0; k < VC; ++k) {
-      float y = (v[k] - mu[k]) * is[k] * gm[k] + bt[k];
-      if constexpr (RES) y += r[k];
-      v[k] = relu ? fmaxf(y, 0.f) : y;
+    for (int i = 0; i < N; ++i) {
+      load_group<T, VC>(x + (m + i * stride) * C + L.c0, v[i]);
+      if constexpr (RES) load_group<T, VC>(res + (m + i * stride) * C + L.c0, r[i]);
     }
-    store_group<T, VC>(out + m * C + L.c0, v);
-  }
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+#pragma unroll
+      for (int k = 0; k < VC; ++k) {
+        float y = (v[i][k] - mu[k]) * is[k] * gm[k] + bt[k];
+        if constexpr (RES) y += r[i][k];
+        v[i][k] = relu ? fmaxf(y, 0.f) : y;
+      }
+      store_group<T, VC>(out + (m + i * stride) * C + L.c0, v[i]);
+    }
+  });
 }
 
 // Plain / JOIN as in whiten_bwd_reduce_nhwc_kernel (JOIN: dout is ga; gamma,
 // beta and relu are unused)
-template <typename T, bool JOIN>
+template <typename T, int VC, int R, bool JOIN>
 __global__ void bn_bwd_reduce_nhwc_kernel(
     const T* __restrict__ x, const T* __restrict__ dout,
     const T* __restrict__ y, const T* __restrict__ gb, T* __restrict__ gid,
@@ -1509,7 +1679,6 @@ __global__ void bn_bwd_reduce_nhwc_kernel(
     const float* __restrict__ istd, const T* __restrict__ gamma,
     const T* __restrict__ beta, float* __restrict__ sums, int C,
     int64_t M, int relu, int has_affine) {
-  constexpr int VC = BnLanes::VC;
   const int part = blockIdx.y;
   const int64_t poff = (int64_t)part * M * C;
   x += poff; dout += poff;
@@ -1520,7 +1689,7 @@ __global__ void bn_bwd_reduce_nhwc_kernel(
   mean += (int64_t)part * C;
   istd += (int64_t)part * C;
   sums += (int64_t)part * 2 * C;
-  const BnLanes L(C);
+  const BnLanes<VC> L(C);
   float mu[VC], is[VC], gm[VC], bt[VC];
 #pragma unroll
   for (int k = 0; k < VC; ++k) {
@@ -1532,36 +1701,44 @@ __global__ void bn_bwd_reduce_nhwc_kernel(
   float s_dy[VC], s_dyxh[VC];
 #pragma unroll
   for (int k = 0; k < VC; ++k) { s_dy[k] = 0.f; s_dyxh[k] = 0.f; }
-  const int64_t stride = L.row_stride();
-  for (int64_t m = L.first_row(); m < M; m += stride) {
-    [[maybe_unused]] const int64_t off = m * C + L.c0;  // JOIN's addressing
-    [[maybe_unused]] float yv[VC];
-    float xv[VC], dv[VC];
-    if constexpr (JOIN) {
-      load_group<T, VC>(x + off, xv);
-      load_group<T, VC>(y + off, yv);
-      join_sum<T, VC>(dout, gb, off, dv);
-    } else {
-      load_group<T, VC>(x + m * C + L.c0, xv);
-      load_group<T, VC>(dout + m * C + L.c0, dv);
+  for_rows<R>(L, M, [&](int64_t m, int64_t stride, auto n) {
+    constexpr int N = decltype(n)::value;
+    [[maybe_unused]] float yv[N][VC];
+    float xv[N][VC], dv[N][VC];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      if constexpr (JOIN) {
+        const int64_t off = (m + i * stride) * C + L.c0;  // JOIN's addressing
+        load_group<T, VC>(x + off, xv[i]);
+        load_group<T, VC>(y + off, yv[i]);
+        join_sum<T, VC>(dout, gb, off, dv[i]);
+      } else {
+        load_group<T, VC>(x + (m + i * stride) * C + L.c0, xv[i]);
+        load_group<T, VC>(dout + (m + i * stride) * C + L.c0, dv[i]);
+      }
     }
 #pragma unroll
-    for (int k = 0; k < VC; ++k) {
-      if constexpr (JOIN) dv[k] = yv[k] > 0.f ? round_to<T>(dv[k]) : 0.f;
-      const float xh = (xv[k] - mu[k]) * is[k];
-      if constexpr (!JOIN) {
-        // relu mask recomputed (sign survives the forward's bf16 store)
-        if (relu && gm[k] * xh + bt[k] <= 0.f) dv[k] = 0.f;
+    for (int i = 0; i < N; ++i) {
+#pragma unroll
+      for (int k = 0; k < VC; ++k) {
+        if constexpr (JOIN)
+          dv[i][k] = yv[i][k] > 0.f ? round_to<T>(dv[i][k]) : 0.f;
+        const float xh = (xv[i][k] - mu[k]) * is[k];
+        if constexpr (!JOIN) {
+          // relu mask recomputed (sign survives the forward's bf16 store)
+          if (relu && gm[k] * xh + bt[k] <= 0.f) dv[i][k] = 0.f;
+        }
+        s_dy[k] += dv[i][k];
+        s_dyxh[k] += dv[i][k] * xh;
       }
-      s_dy[k] += dv[k];
-      s_dyxh[k] += dv[k] * xh;
+      if constexpr (JOIN)
+        store_group<T, VC>(gid + (m + i * stride) * C + L.c0, dv[i]);
     }
-    if constexpr (JOIN) store_group<T, VC>(gid + off, dv);
-  }
+  });
   bn_two_sum_flush(L, C, s_dy, s_dyxh, sums);
 }
 
-template <typename T>
+template <typename T, int VC, int R>
 __global__ void bn_bwd_apply_nhwc_kernel(
     const T* __restrict__ x, const T* __restrict__ dout,
     const float* __restrict__ mean,
@@ -1569,14 +1746,13 @@ __global__ void bn_bwd_apply_nhwc_kernel(
     const T* __restrict__ beta,
     const float* __restrict__ sums, T* __restrict__ dx, int C, int64_t M,
     float inv_m, int relu, int has_affine, int use_batch) {
-  constexpr int VC = BnLanes::VC;
   const int part = blockIdx.y;
   const int64_t poff = (int64_t)part * M * C;
   x += poff; dout += poff; dx += poff;
   mean += (int64_t)part * C;
   istd += (int64_t)part * C;
   sums += (int64_t)part * 2 * C;
-  const BnLanes L(C);
+  const BnLanes<VC> L(C);
   float mu[VC], is[VC], gm[VC], bt[VC], mdy[VC], mdyxh[VC];
 #pragma unroll
   for (int k = 0; k < VC; ++k) {
@@ -1588,24 +1764,30 @@ __global__ void bn_bwd_apply_nhwc_kernel(
     mdy[k] = use_batch ? sums[c] * inv_m : 0.f;
     mdyxh[k] = use_batch ? sums[C + c] * inv_m : 0.f;
   }
-  const int64_t stride = L.row_stride();
-  for (int64_t m = L.first_row(); m < M; m += stride) {
-    float xv[VC], dv[VC];
-    load_group<T, VC>(x + m * C + L.c0, xv);
-    load_group<T, VC>(dout + m * C + L.c0, dv);
+  for_rows<R>(L, M, [&](int64_t m, int64_t stride, auto n) {
+    constexpr int N = decltype(n)::value;
+    float xv[N][VC], dv[N][VC];
 #pragma unroll
-    for (int k = 0; k < VC; ++k) {
-      const float xh = (xv[k] - mu[k]) * is[k];
-      if (relu && gm[k] * xh + bt[k] <= 0.f) dv[k] = 0.f;
-      const float dxh = dv[k] * gm[k];
-      if (use_batch) {
-        dv[k] = (dxh - gm[k] * mdy[k] - xh * gm[k] * mdyxh[k]) * is[k];
-      } else {
-        dv[k] = dxh * is[k];
-      }
+    for (int i = 0; i < N; ++i) {
+      load_group<T, VC>(x + (m + i * stride) * C + L.c0, xv[i]);
+      load_group<T, VC>(dout + (m + i * stride) * C + L.c0, dv[i]);
     }
-    store_group<T, VC>(dx + m * C + L.c0, dv);
-  }
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+#pragma unroll
+      for (int k = 0; k < VC; ++k) {
+        const float xh = (xv[i][k] - mu[k]) * is[k];
+        if (relu && gm[k] * xh + bt[k] <= 0.f) dv[i][k] = 0.f;
+        const float dxh = dv[i][k] * gm[k];
+        if (use_batch) {
+          dv[i][k] = (dxh - gm[k] * mdy[k] - xh * gm[k] * mdyxh[k]) * is[k];
+        } else {
+          dv[i][k] = dxh * is[k];
+        }
+      }
+      store_group<T, VC>(dx + (m + i * stride) * C + L.c0, dv[i]);
+    }
+  });
 }
 
 // ===========================================================================
@@ -2323,10 +2505,10 @@ void whiten_stats(Tensor x, Tensor acc, Tensor mean, Tensor cov, int64_t g) {
 
 // Group sizes 2 and 4 only — the NHWC route never takes g=8 (it spills; see
 // hip_ops.whiten_cl_supported).
-#define DWT_SWITCH_G(g, body)                                                  \
+#define DWT_SWITCH_G(g, ...)                                                   \
   switch (g) {                                                                 \
-    case 2: { constexpr int G = 2; body; break; }                              \
-    case 4: { constexpr int G = 4; body; break; }                              \
+    case 2: { constexpr int G = 2; __VA_ARGS__; break; }                       \
+    case 4: { constexpr int G = 4; __VA_ARGS__; break; }                       \
     default: TORCH_CHECK(false, "unsupported group size ", g);                 \
   }
 
@@ -2344,24 +2526,133 @@ inline int64_t nhwc_elem_blocks(int64_t M, int rows_per_iter, int zslices) {
 
 // Grid of a 256-thread NHWC kernel (see WhitenLanes / BnLanes): x = blocks of
 // position rows, y = parts, z = slices of `slice` channels, each row of a
-// slice taking min(C, slice) / vec lanes.
+// slice taking min(C, slice) / vec lanes and each lane `rows` rows per loop
+// iteration.
 inline dim3 nhwc_grid(bool reduce, int64_t C, int64_t M, int64_t parts,
-                      int slice, int vec) {
+                      int slice, int vec, int rows) {
   const int zslices = (C + slice - 1) / slice;
   const int lanes = std::min<int64_t>(C, slice) / vec;
-  const int rows_per_iter = std::max(256 / lanes, 1);
+  const int rows_per_iter = std::max(256 / lanes, 1) * rows;
   const int64_t blocks =
       reduce ? nhwc_reduce_blocks(M, rows_per_iter, zslices * parts)
              : nhwc_elem_blocks(M, rows_per_iter, zslices * parts);
   return dim3(blocks, parts, zslices);
 }
-inline dim3 whiten_grid(bool reduce, int G, int64_t C, int64_t M, int64_t parts) {
-  return nhwc_grid(reduce, C, M, parts, 256, G);
+// wide: the lane-pair form (WhitenRows), a lane per group and two rows per
+// iteration — the narrow form's block count would leave half the blocks idle
+inline dim3 whiten_grid(bool reduce, int G, int64_t C, int64_t M, int64_t parts,
+                        bool wide = false) {
+  return nhwc_grid(reduce, C, M, parts, 256, G, wide ? 2 : 1);
 }
-inline dim3 bn_grid(bool reduce, int64_t C, int64_t M, int64_t parts) {
-  return nhwc_grid(reduce, C, M, parts, 1024, dwt::BnLanes::VC);
+inline dim3 bn_grid(bool reduce, int64_t C, int64_t M, int64_t parts, int vc,
+                    int rows) {
+  return nhwc_grid(reduce, C, M, parts, 1024, vc, rows);
 }
 constexpr bool kReduce = true, kElem = false;
+
+// ---- 16-byte accesses for bf16 (DWT_AMD_NORM_WIDE, docs/KERNELS.md) ----
+// The bf16 NHWC norm kernels have a wide form that moves 16 bytes per lane
+// access: 8-channel chunks in the BN family, lane pairs in g=4 whitening.
+// A launcher takes it when the switch is on, C and the lane map allow it and
+// every streamed pointer is 16-byte aligned (a channels_last view into a
+// larger buffer may not be); otherwise it launches the narrow form, which
+// serves every shape the Python side admits.
+static bool g_norm_wide = true;
+void set_norm_wide(bool on) { g_norm_wide = on; }
+
+template <typename Ptrs>
+inline bool aligned16(const Ptrs& ptrs) {
+  for (const void* p : ptrs)
+    if (reinterpret_cast<uintptr_t>(p) % 16 != 0) return false;  // null passes
+  return true;
+}
+inline const void* raw_ptr(const Tensor& t) { return t.data_ptr(); }
+inline const void* raw_ptr(const c10::optional<Tensor>& t) {
+  return t.has_value() ? t->data_ptr() : nullptr;
+}
+
+template <typename T> constexpr bool kIsBf16 = std::is_same_v<T, c10::BFloat16>;
+
+using PtrList = std::initializer_list<const void*>;
+template <typename Ptrs = PtrList>
+inline bool bn_wide(int64_t C, const Ptrs& streamed) {
+  if (!g_norm_wide || C % 8 != 0) return false;
+  const int64_t lanes = std::min<int64_t>(C, 1024) / 8;
+  return 256 % lanes == 0 && aligned16(streamed);
+}
+template <typename Ptrs = PtrList>
+inline bool whiten_wide(int64_t g, int64_t C, const Ptrs& streamed) {
+  return g_norm_wide && g == 4 && C % 8 == 0 && aligned16(streamed);
+}
+
+// Whether a launch over these streamed tensors may take the wide form: kind
+// "bn" or "whiten" (g ignored for bn).  For tests and benchmarks; the
+// launchers decide by the same predicates, then by whether the kernel has
+// its wide form in use (kBn*Wide / kWhiten*Wide below).
+bool norm_wide_selected(const std::string& kind, std::vector<Tensor> streamed,
+                        int64_t g, int64_t C) {
+  std::vector<const void*> ptrs;
+  for (const Tensor& t : streamed) {
+    if (t.scalar_type() != at::ScalarType::BFloat16) return false;
+    ptrs.push_back(t.data_ptr());
+  }
+  TORCH_CHECK(kind == "bn" || kind == "whiten", "norm_wide_selected: kind ", kind);
+  return kind == "bn" ? bn_wide(C, ptrs) : whiten_wide(g, C, ptrs);
+}
+
+// Rows per lane per loop iteration of the wide BN kernels (for_rows), chosen
+// for 32-64 KiB of loads in flight per CU at the occupancy of
+// profiles/kernel_resources.md: 16 B x operands x rows x 64 lanes x waves.
+constexpr int kBnStatsRows = 2;      // 1 operand
+constexpr int kBnApplyRows = 2;      // 1 operand
+constexpr int kBnApplyResRows = 1;   // 2 operands
+constexpr int kBnReduceRows = 1;     // 2 operands (JOIN: 3 or 4)
+constexpr int kBnBwdApplyRows = 1;   // 2 operands
+
+// Which kernels have their wide form in use: the ones that measured faster
+// wide in the flagship step (profiles/r50_step_norm_wide.md).  The 8-channel
+// BN kernels that carry per-channel parameters pay for the width in
+// registers (occupancy 8 -> 5-7) and lost; both join reduces were no
+// faster.  A kernel switched off here is launched narrow whatever bn_wide /
+// whiten_wide say, and its wide form is not instantiated.
+constexpr bool kBnStatsWide = true;
+constexpr bool kBnApplyWide = false;        // 3.48 -> 4.23 ms per step
+constexpr bool kBnApplyResWide = true;
+constexpr bool kBnReduceWide = false;       // 4.55 -> 5.23
+constexpr bool kBnJoinReduceWide = false;   // 8.97 -> 9.05
+constexpr bool kBnBwdApplyWide = false;     // 11.14 -> 14.16
+constexpr bool kWhitenStatsWide = true;
+constexpr bool kWhitenApplyWide = true;     // with and without res
+constexpr bool kWhitenReduceWide = true;
+constexpr bool kWhitenJoinReduceWide = false;  // 6.76 -> 6.96
+constexpr bool kWhitenBwdApplyWide = true;
+
+// Launches f(integral_constant VC, integral_constant R): the wide form
+// (VC = 8, R = Rows) for bf16 where `wide` and the kernel has it in use,
+// else the narrow VC = 4, R = 1 (the only form of fp32).
+template <typename T, int Rows, bool InUse, typename F>
+inline void bn_launch(bool wide, F&& f) {
+  if constexpr (kIsBf16<T> && InUse) {
+    if (wide) {
+      f(std::integral_constant<int, 8>{}, std::integral_constant<int, Rows>{});
+      return;
+    }
+  }
+  f(std::integral_constant<int, 4>{}, std::integral_constant<int, 1>{});
+}
+
+// Launches f(bool_constant WIDE): the lane-pair form (WhitenRows) for bf16
+// g=4 where `wide` and the kernel has it in use, else the narrow form.
+template <typename T, int G, bool InUse, typename F>
+inline void whiten_launch(bool wide, F&& f) {
+  if constexpr (kIsBf16<T> && G == 4 && InUse) {
+    if (wide) {
+      f(std::true_type{});
+      return;
+    }
+  }
+  f(std::false_type{});
+}
 
 // null for an operand the kernels treat as optional (gamma / beta without an
 // affine, the join's second consumer)
@@ -2381,10 +2672,13 @@ void whiten_stats_partial_cl(Tensor x, Tensor acc, int64_t g, int64_t C,
                              int64_t M, int64_t parts) {
   DISPATCH_FT(x, "whiten_stats_cl", [&] {
     DWT_SWITCH_G(g, {
-      hipLaunchKernelGGL((dwt::whiten_stats_nhwc_kernel<scalar_t, G>),
-                         whiten_grid(kReduce, G, C, M, parts), dim3(256), 0,
-                         cur_stream(), x.data_ptr<scalar_t>(),
-                         acc.data_ptr<float>(), (int)C, M);
+      whiten_launch<scalar_t, G, kWhitenStatsWide>(whiten_wide(g, C, {raw_ptr(x)}), [&](auto w) {
+        constexpr bool WIDE = decltype(w)::value;
+        hipLaunchKernelGGL((dwt::whiten_stats_nhwc_kernel<scalar_t, G, WIDE>),
+                           whiten_grid(kReduce, G, C, M, parts, WIDE),
+                           dim3(256), 0, cur_stream(), x.data_ptr<scalar_t>(),
+                           acc.data_ptr<float>(), (int)C, M);
+      });
     });
   });
 }
@@ -2421,17 +2715,21 @@ void whiten_apply_res_cl(Tensor x, Tensor mean, Tensor W, Tensor gamma,
               "whiten_apply_res_cl: res mismatch");
   DISPATCH_FT(x, "whiten_apply_cl", [&] {
     DWT_SWITCH_G(g, {
+      const bool wide =
+          whiten_wide(g, C, {raw_ptr(x), raw_ptr(res), raw_ptr(out)});
       auto launch = [&](auto with_res) {
         constexpr bool RES = decltype(with_res)::value;
-        hipLaunchKernelGGL((dwt::whiten_apply_nhwc_kernel<scalar_t, G, RES>),
-                           whiten_grid(kElem, G, C, M, parts), dim3(256), 0,
-                           cur_stream(), x.data_ptr<scalar_t>(),
-                           opt_ptr<scalar_t>(res), mean.data_ptr<float>(),
-                           W.data_ptr<float>(),
-                           opt_ptr<scalar_t>(gamma, has_affine),
-                           opt_ptr<scalar_t>(beta, has_affine),
-                           out.data_ptr<scalar_t>(), (int)C, M, relu ? 1 : 0,
-                           has_affine ? 1 : 0);
+        whiten_launch<scalar_t, G, kWhitenApplyWide>(wide, [&](auto w) {
+          constexpr bool WIDE = decltype(w)::value;
+          hipLaunchKernelGGL(
+              (dwt::whiten_apply_nhwc_kernel<scalar_t, G, WIDE, RES>),
+              whiten_grid(kElem, G, C, M, parts, WIDE), dim3(256), 0,
+              cur_stream(), x.data_ptr<scalar_t>(), opt_ptr<scalar_t>(res),
+              mean.data_ptr<float>(), W.data_ptr<float>(),
+              opt_ptr<scalar_t>(gamma, has_affine),
+              opt_ptr<scalar_t>(beta, has_affine), out.data_ptr<scalar_t>(),
+              (int)C, M, relu ? 1 : 0, has_affine ? 1 : 0);
+        });
       };
       if (res.has_value()) launch(std::true_type{});
       else launch(std::false_type{});
@@ -2467,15 +2765,20 @@ void whiten_bwd_reduce_cl(Tensor x, Tensor dout, Tensor mean,
                           bool has_affine, int64_t parts) {
   DISPATCH_FT(x, "whiten_bwd_reduce_cl", [&] {
     DWT_SWITCH_G(g, {
-      hipLaunchKernelGGL(
-          (dwt::whiten_bwd_reduce_nhwc_kernel<scalar_t, G, false>),
-          whiten_grid(kReduce, G, C, M, parts), dim3(256), 0, cur_stream(),
-          x.data_ptr<scalar_t>(), dout.data_ptr<scalar_t>(),
-          (const scalar_t*)nullptr, (const scalar_t*)nullptr,
-          (scalar_t*)nullptr, mean.data_ptr<float>(), W.data_ptr<float>(),
-          opt_ptr<scalar_t>(gamma, has_affine),
-          opt_ptr<scalar_t>(beta, has_affine), dWacc.data_ptr<float>(),
-          dgb.data_ptr<float>(), (int)C, M, relu ? 1 : 0, has_affine ? 1 : 0);
+      const bool wide = whiten_wide(g, C, {raw_ptr(x), raw_ptr(dout)});
+      whiten_launch<scalar_t, G, kWhitenReduceWide>(wide, [&](auto w) {
+        constexpr bool WIDE = decltype(w)::value;
+        hipLaunchKernelGGL(
+            (dwt::whiten_bwd_reduce_nhwc_kernel<scalar_t, G, WIDE, false>),
+            whiten_grid(kReduce, G, C, M, parts, WIDE), dim3(256), 0,
+            cur_stream(), x.data_ptr<scalar_t>(), dout.data_ptr<scalar_t>(),
+            (const scalar_t*)nullptr, (const scalar_t*)nullptr,
+            (scalar_t*)nullptr, mean.data_ptr<float>(), W.data_ptr<float>(),
+            opt_ptr<scalar_t>(gamma, has_affine),
+            opt_ptr<scalar_t>(beta, has_affine), dWacc.data_ptr<float>(),
+            dgb.data_ptr<float>(), (int)C, M, relu ? 1 : 0,
+            has_affine ? 1 : 0);
+      });
     });
   });
 }
@@ -2489,15 +2792,20 @@ void whiten_join_bwd_reduce_cl(Tensor x, Tensor y, Tensor ga,
                   parts * M * C);
   DISPATCH_FT(x, "whiten_join_bwd_reduce_cl", [&] {
     DWT_SWITCH_G(g, {
-      hipLaunchKernelGGL(
-          (dwt::whiten_bwd_reduce_nhwc_kernel<scalar_t, G, true>),
-          whiten_grid(kReduce, G, C, M, parts), dim3(256), 0, cur_stream(),
-          x.data_ptr<scalar_t>(), ga.data_ptr<scalar_t>(),
-          y.data_ptr<scalar_t>(), opt_ptr<scalar_t>(gb),
-          gid.data_ptr<scalar_t>(), mean.data_ptr<float>(),
-          W.data_ptr<float>(), opt_ptr<scalar_t>(gamma, has_affine),
-          (const scalar_t*)nullptr, dWacc.data_ptr<float>(),
-          dgb.data_ptr<float>(), (int)C, M, 0, has_affine ? 1 : 0);
+      const bool wide = whiten_wide(
+          g, C, {raw_ptr(x), raw_ptr(y), raw_ptr(ga), raw_ptr(gb), raw_ptr(gid)});
+      whiten_launch<scalar_t, G, kWhitenJoinReduceWide>(wide, [&](auto w) {
+        constexpr bool WIDE = decltype(w)::value;
+        hipLaunchKernelGGL(
+            (dwt::whiten_bwd_reduce_nhwc_kernel<scalar_t, G, WIDE, true>),
+            whiten_grid(kReduce, G, C, M, parts, WIDE), dim3(256), 0,
+            cur_stream(), x.data_ptr<scalar_t>(), ga.data_ptr<scalar_t>(),
+            y.data_ptr<scalar_t>(), opt_ptr<scalar_t>(gb),
+            gid.data_ptr<scalar_t>(), mean.data_ptr<float>(),
+            W.data_ptr<float>(), opt_ptr<scalar_t>(gamma, has_affine),
+            (const scalar_t*)nullptr, dWacc.data_ptr<float>(),
+            dgb.data_ptr<float>(), (int)C, M, 0, has_affine ? 1 : 0);
+      });
     });
   });
 }
@@ -2509,16 +2817,20 @@ void whiten_bwd_apply_cl(Tensor x, Tensor dout, Tensor mean,
                          bool has_affine, bool train_stats, int64_t parts) {
   DISPATCH_FT(x, "whiten_bwd_apply_cl", [&] {
     DWT_SWITCH_G(g, {
-      hipLaunchKernelGGL((dwt::whiten_bwd_apply_nhwc_kernel<scalar_t, G>),
-                         whiten_grid(kElem, G, C, M, parts), dim3(256), 0,
-                         cur_stream(), x.data_ptr<scalar_t>(),
-                         dout.data_ptr<scalar_t>(),
-                         mean.data_ptr<float>(), W.data_ptr<float>(),
-                         opt_ptr<scalar_t>(gamma, has_affine),
-                         opt_ptr<scalar_t>(beta, has_affine),
-                         S.data_ptr<float>(), corr.data_ptr<float>(),
-                         dx.data_ptr<scalar_t>(), (int)C, M, relu ? 1 : 0,
-                         has_affine ? 1 : 0, train_stats ? 1 : 0);
+      const bool wide =
+          whiten_wide(g, C, {raw_ptr(x), raw_ptr(dout), raw_ptr(dx)});
+      whiten_launch<scalar_t, G, kWhitenBwdApplyWide>(wide, [&](auto w) {
+        constexpr bool WIDE = decltype(w)::value;
+        hipLaunchKernelGGL(
+            (dwt::whiten_bwd_apply_nhwc_kernel<scalar_t, G, WIDE>),
+            whiten_grid(kElem, G, C, M, parts, WIDE), dim3(256), 0,
+            cur_stream(), x.data_ptr<scalar_t>(), dout.data_ptr<scalar_t>(),
+            mean.data_ptr<float>(), W.data_ptr<float>(),
+            opt_ptr<scalar_t>(gamma, has_affine),
+            opt_ptr<scalar_t>(beta, has_affine), S.data_ptr<float>(),
+            corr.data_ptr<float>(), dx.data_ptr<scalar_t>(), (int)C, M,
+            relu ? 1 : 0, has_affine ? 1 : 0, train_stats ? 1 : 0);
+      });
     });
   });
 }
@@ -2526,10 +2838,13 @@ void whiten_bwd_apply_cl(Tensor x, Tensor dout, Tensor mean,
 void bn_stats_partial_cl(Tensor x, Tensor acc, int64_t C, int64_t M,
                          int64_t parts) {
   DISPATCH_FT(x, "bn_stats_cl", [&] {
-    hipLaunchKernelGGL((dwt::bn_stats_nhwc_kernel<scalar_t>),
-                       bn_grid(kReduce, C, M, parts), dim3(256), 0,
-                       cur_stream(), x.data_ptr<scalar_t>(),
-                       acc.data_ptr<float>(), (int)C, M);
+    bn_launch<scalar_t, kBnStatsRows, kBnStatsWide>(bn_wide(C, {raw_ptr(x)}), [&](auto vc, auto rows) {
+      constexpr int VC = decltype(vc)::value, R = decltype(rows)::value;
+      hipLaunchKernelGGL((dwt::bn_stats_nhwc_kernel<scalar_t, VC, R>),
+                         bn_grid(kReduce, C, M, parts, VC, R), dim3(256), 0,
+                         cur_stream(), x.data_ptr<scalar_t>(),
+                         acc.data_ptr<float>(), (int)C, M);
+    });
   });
 }
 
@@ -2558,20 +2873,27 @@ void bn_apply_res_cl(Tensor x, Tensor mean, Tensor istd, Tensor gamma,
                                    res->numel() == x.numel()),
               "bn_apply_res_cl: res mismatch");
   DISPATCH_FT(x, "bn_apply_cl", [&] {
-    auto launch = [&](auto with_res) {
+    const bool wide = bn_wide(C, {raw_ptr(x), raw_ptr(res), raw_ptr(out)});
+    auto launch = [&](auto with_res, auto wide_rows) {
       constexpr bool RES = decltype(with_res)::value;
-      hipLaunchKernelGGL((dwt::bn_apply_nhwc_kernel<scalar_t, RES>),
-                         bn_grid(kElem, C, M, parts), dim3(256), 0,
-                         cur_stream(), x.data_ptr<scalar_t>(),
-                         opt_ptr<scalar_t>(res), mean.data_ptr<float>(),
-                         istd.data_ptr<float>(),
-                         opt_ptr<scalar_t>(gamma, has_affine),
-                         opt_ptr<scalar_t>(beta, has_affine),
-                         out.data_ptr<scalar_t>(), (int)C, M, relu ? 1 : 0,
+      constexpr bool kInUse = RES ? kBnApplyResWide : kBnApplyWide;
+      bn_launch<scalar_t, decltype(wide_rows)::value, kInUse>(wide, [&](auto vc, auto rows) {
+        constexpr int VC = decltype(vc)::value, R = decltype(rows)::value;
+        hipLaunchKernelGGL((dwt::bn_apply_nhwc_kernel<scalar_t, VC, R, RES>),
+                           bn_grid(kElem, C, M, parts, VC, R), dim3(256), 0,
+                           cur_stream(), x.data_ptr<scalar_t>(),
+                           opt_ptr<scalar_t>(res), mean.data_ptr<float>(),
+                           istd.data_ptr<float>(),
+                           opt_ptr<scalar_t>(gamma, has_affine),
+                           opt_ptr<scalar_t>(beta, has_affine),
+                           out.data_ptr<scalar_t>(), (int)C, M, relu ? 1 : 0,
                            has_affine ? 1 : 0);
+      });
     };
-    if (res.has_value()) launch(std::true_type{});
-    else launch(std::false_type{});
+    if (res.has_value())
+      launch(std::true_type{}, std::integral_constant<int, kBnApplyResRows>{});
+    else
+      launch(std::false_type{}, std::integral_constant<int, kBnApplyRows>{});
   });
 }
 
@@ -2587,15 +2909,19 @@ void bn_bwd_reduce_cl(Tensor x, Tensor dout, Tensor mean,
                       Tensor sums, int64_t C, int64_t M,
                       bool relu, bool has_affine, int64_t parts) {
   DISPATCH_FT(x, "bn_bwd_reduce_cl", [&] {
-    hipLaunchKernelGGL(
-        (dwt::bn_bwd_reduce_nhwc_kernel<scalar_t, false>),
-        bn_grid(kReduce, C, M, parts), dim3(256), 0, cur_stream(),
-        x.data_ptr<scalar_t>(), dout.data_ptr<scalar_t>(),
-        (const scalar_t*)nullptr, (const scalar_t*)nullptr, (scalar_t*)nullptr,
-        mean.data_ptr<float>(), istd.data_ptr<float>(),
-        opt_ptr<scalar_t>(gamma, has_affine),
-        opt_ptr<scalar_t>(beta, has_affine), sums.data_ptr<float>(), (int)C, M,
-        relu ? 1 : 0, has_affine ? 1 : 0);
+    const bool wide = bn_wide(C, {raw_ptr(x), raw_ptr(dout)});
+    bn_launch<scalar_t, kBnReduceRows, kBnReduceWide>(wide, [&](auto vc, auto rows) {
+      constexpr int VC = decltype(vc)::value, R = decltype(rows)::value;
+      hipLaunchKernelGGL(
+          (dwt::bn_bwd_reduce_nhwc_kernel<scalar_t, VC, R, false>),
+          bn_grid(kReduce, C, M, parts, VC, R), dim3(256), 0, cur_stream(),
+          x.data_ptr<scalar_t>(), dout.data_ptr<scalar_t>(),
+          (const scalar_t*)nullptr, (const scalar_t*)nullptr,
+          (scalar_t*)nullptr, mean.data_ptr<float>(), istd.data_ptr<float>(),
+          opt_ptr<scalar_t>(gamma, has_affine),
+          opt_ptr<scalar_t>(beta, has_affine), sums.data_ptr<float>(), (int)C,
+          M, relu ? 1 : 0, has_affine ? 1 : 0);
+    });
   });
 }
 
@@ -2605,14 +2931,19 @@ void bn_join_bwd_reduce_cl(Tensor x, Tensor y, Tensor ga,
                            int64_t parts) {
   check_join_args("bn_join_bwd_reduce_cl", x, y, ga, gb, gid, parts * M * C);
   DISPATCH_FT(x, "bn_join_bwd_reduce_cl", [&] {
-    hipLaunchKernelGGL(
-        (dwt::bn_bwd_reduce_nhwc_kernel<scalar_t, true>),
-        bn_grid(kReduce, C, M, parts), dim3(256), 0, cur_stream(),
-        x.data_ptr<scalar_t>(), ga.data_ptr<scalar_t>(),
-        y.data_ptr<scalar_t>(), opt_ptr<scalar_t>(gb), gid.data_ptr<scalar_t>(),
-        mean.data_ptr<float>(), istd.data_ptr<float>(),
-        (const scalar_t*)nullptr, (const scalar_t*)nullptr,
-        sums.data_ptr<float>(), (int)C, M, 0, 0);
+    const bool wide = bn_wide(
+        C, {raw_ptr(x), raw_ptr(y), raw_ptr(ga), raw_ptr(gb), raw_ptr(gid)});
+    bn_launch<scalar_t, kBnReduceRows, kBnJoinReduceWide>(wide, [&](auto vc, auto rows) {
+      constexpr int VC = decltype(vc)::value, R = decltype(rows)::value;
+      hipLaunchKernelGGL(
+          (dwt::bn_bwd_reduce_nhwc_kernel<scalar_t, VC, R, true>),
+          bn_grid(kReduce, C, M, parts, VC, R), dim3(256), 0, cur_stream(),
+          x.data_ptr<scalar_t>(), ga.data_ptr<scalar_t>(),
+          y.data_ptr<scalar_t>(), opt_ptr<scalar_t>(gb),
+          gid.data_ptr<scalar_t>(), mean.data_ptr<float>(),
+          istd.data_ptr<float>(), (const scalar_t*)nullptr,
+          (const scalar_t*)nullptr, sums.data_ptr<float>(), (int)C, M, 0, 0);
+    });
   });
 }
 
@@ -2622,15 +2953,20 @@ void bn_bwd_apply_cl(Tensor x, Tensor dout, Tensor mean,
                      int64_t C, int64_t M, bool relu, bool has_affine,
                      bool use_batch, int64_t parts, int64_t count) {
   DISPATCH_FT(x, "bn_bwd_apply_cl", [&] {
-    hipLaunchKernelGGL((dwt::bn_bwd_apply_nhwc_kernel<scalar_t>),
-                       bn_grid(kElem, C, M, parts), dim3(256), 0, cur_stream(),
-                       x.data_ptr<scalar_t>(), dout.data_ptr<scalar_t>(),
-                       mean.data_ptr<float>(), istd.data_ptr<float>(),
-                       opt_ptr<scalar_t>(gamma, has_affine),
-                       opt_ptr<scalar_t>(beta, has_affine),
-                       sums.data_ptr<float>(), dx.data_ptr<scalar_t>(), (int)C,
-                       M, 1.0f / (float)count, relu ? 1 : 0,
-                       has_affine ? 1 : 0, use_batch ? 1 : 0);
+    const bool wide = bn_wide(C, {raw_ptr(x), raw_ptr(dout), raw_ptr(dx)});
+    bn_launch<scalar_t, kBnBwdApplyRows, kBnBwdApplyWide>(wide, [&](auto vc, auto rows) {
+      constexpr int VC = decltype(vc)::value, R = decltype(rows)::value;
+      hipLaunchKernelGGL((dwt::bn_bwd_apply_nhwc_kernel<scalar_t, VC, R>),
+                         bn_grid(kElem, C, M, parts, VC, R), dim3(256), 0,
+                         cur_stream(), x.data_ptr<scalar_t>(),
+                         dout.data_ptr<scalar_t>(), mean.data_ptr<float>(),
+                         istd.data_ptr<float>(),
+                         opt_ptr<scalar_t>(gamma, has_affine),
+                         opt_ptr<scalar_t>(beta, has_affine),
+                         sums.data_ptr<float>(), dx.data_ptr<scalar_t>(),
+                         (int)C, M, 1.0f / (float)count, relu ? 1 : 0,
+                         has_affine ? 1 : 0, use_batch ? 1 : 0);
+    });
   });
 }
 
@@ -3211,6 +3547,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_apply_res_cl", &bn_apply_res_cl);
   m.def("whiten_join_bwd_reduce_cl", &whiten_join_bwd_reduce_cl);
   m.def("bn_join_bwd_reduce_cl", &bn_join_bwd_reduce_cl);
+  m.def("set_norm_wide", &set_norm_wide);
+  m.def("norm_wide_selected", &norm_wide_selected);
   m.def("matfn_chol_fwd", &matfn_chol_fwd);
   m.def("matfn_chol_bwd", &matfn_chol_bwd);
   m.def("matfn_ns_fwd", &matfn_ns_fwd);
