@@ -152,6 +152,13 @@ def _train_loop(args, model, device, source_iter, target_iter,
     print("Running a bunch of forward passes to estimate the population statistics of target...")
     eval_pass_collect_stats(args, model, device, target_test_loader,
                             passes=stats_passes, batcher=batcher)
+    export_path = getattr(args, "export_folded", "")
+    dist = torch.distributed
+    if export_path and not (dist.is_available() and dist.is_initialized()
+                            and dist.get_rank() != 0):
+        from ..models.folded import fold_resnet
+        ckpt.save_folded(export_path, fold_resnet(model))
+        print(f"folded inference checkpoint written: {export_path}")
     print("Finally computing the precision on the test set...")
     return test(args, model, device, target_test_loader, logger=logger,
                 batcher=batcher)
@@ -159,6 +166,12 @@ def _train_loop(args, model, device, source_iter, target_iter,
 
 def test(args, model, device, target_test_loader, logger: JsonlLogger = None,
          batcher=None):
+    if getattr(args, "folded_eval", False):
+        # --folded_eval: a fresh snapshot of the current statistics with every
+        # norm site folded into its conv (models/folded.py)
+        from ..models.folded import FoldedResNetDWT, fold_resnet
+        if not isinstance(model, FoldedResNetDWT):
+            model = fold_resnet(model)
     model.eval()
     test_loss = 0.0
     correct = 0

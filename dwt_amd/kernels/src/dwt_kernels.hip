@@ -3503,6 +3503,12 @@ void mfma_conv2d_fwd(torch::Tensor x, torch::Tensor wgt, torch::Tensor bias,
                      int64_t Cin, int64_t P, int64_t Q, int64_t Cout,
                      int64_t KH, int64_t KW, int64_t stride, int64_t pad,
                      bool relu, bool has_bias);
+void mfma_conv2d_fwd_fused(torch::Tensor x, torch::Tensor wgt,
+                           torch::Tensor bias, torch::Tensor res,
+                           torch::Tensor out, int64_t N, int64_t H, int64_t W,
+                           int64_t Cin, int64_t P, int64_t Q, int64_t Cout,
+                           int64_t KH, int64_t KW, int64_t stride, int64_t pad,
+                           bool relu, bool has_res);
 void conv1x1_stats(torch::Tensor x, torch::Tensor wgt, torch::Tensor out,
                    torch::Tensor acc, int64_t kind, int64_t g, int64_t parts,
                    int64_t max_workgroups);
@@ -3525,6 +3531,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("assemble_views", &assemble_views);
   m.def("mfma_gemm", &mfma_gemm);
   m.def("mfma_conv2d_fwd", &mfma_conv2d_fwd);
+  m.def("mfma_conv2d_fwd_fused", &mfma_conv2d_fwd_fused);
   m.def("conv1x1_stats", &conv1x1_stats);
   m.def("mfma_conv2d_dgrad", &mfma_conv2d_dgrad);
   m.def("mfma_conv2d_wgrad", &mfma_conv2d_wgrad);

@@ -14,7 +14,9 @@
 //   128x128 block tile, BK=64, 4 waves each computing a 64x64 sub-tile as
 //   4x4 fragments of v_mfma_f32_16x16x32_bf16; A/B tiles staged via
 //   registers into LDS with +16B row padding (bank-conflict fix, §6 G4);
-//   fp32 accumulate; fused bias + ReLU epilogue, bf16 store.
+//   fp32 accumulate; fused bias + ReLU epilogue, bf16 store.  The folded-
+//   inference entry (conv_fused_fwd_kernel) runs the same tile body with a
+//   bias + residual + ReLU epilogue staged through LDS (16-byte stores).
 //
 // A-fragment layout for mfma_f32_16x16x32_bf16 (cdna4_isa.md §10):
 //   lane l holds A[row = l%16][k = (l/16)*8 + j], j = 0..7  (one b128 read)
@@ -287,14 +289,28 @@ DEV_INLINE void write_tile(const StageRegs& rg, unsigned short* lds) {
 // single-buffer loop wins for short-K and for the implicit gather path
 // (within-shape A/B on the R50 shapes).  SWZ: XCD-aware bijective block
 // remap (guide T1) — only when the grid has several N-tiles to share.
-template <int MODE, bool RELU, bool HAS_BIAS, bool PIPE, bool SWZ>
-__global__ __launch_bounds__(THREADS, PIPE ? 2 : 3) void conv_implicit_gemm_kernel(
-    const bf16* __restrict__ x, const bf16* __restrict__ wgt,
-    const float* __restrict__ bias, bf16* __restrict__ out, ConvParams cp,
-    int mtiles, int ntiles) {
-  __shared__ unsigned short lds_a[PIPE ? 2 : 1][BM * LDS_PITCH];
-  __shared__ unsigned short lds_b[PIPE ? 2 : 1][BN * LDS_PITCH];
+//
+// One tile body serves two kernels.  EPI_NARROW is the training-path
+// epilogue (optional bias / ReLU, 2-byte stores in the fragment layout).
+// EPI_WIDE / EPI_WIDE_RES are the folded-inference epilogue: bias always,
+// optional residual and ReLU, fp32 adds and ONE rounding, the C tile staged
+// over the A/B LDS storage and written as 16-byte row-contiguous stores.
+enum Epilogue { EPI_NARROW = 0, EPI_WIDE = 1, EPI_WIDE_RES = 2 };
 
+constexpr int C_PITCH = BN + PAD_HALFS;  // C staging row pitch (halves)
+constexpr int TILE_HALFS = BM * LDS_PITCH;
+static_assert(BM == BN, "A and B tiles share TILE_HALFS");
+static_assert(BM * C_PITCH <= 2 * TILE_HALFS,
+              "C staging must fit the A/B storage");
+
+// lds: [buf][a|b][TILE_HALFS], 16-byte aligned; the wide epilogues overlay
+// the C tile on it from offset 0.
+template <int MODE, bool RELU, bool HAS_BIAS, bool PIPE, bool SWZ, int EPI>
+DEV_INLINE void conv_gemm_tile(
+    const bf16* __restrict__ x, const bf16* __restrict__ wgt,
+    const float* __restrict__ bias, const bf16* __restrict__ res,
+    bf16* __restrict__ out, const ConvParams& cp, int mtiles, int ntiles,
+    unsigned short* lds) {
   int bid = blockIdx.x;
   if (SWZ) {
     const int nwg = mtiles * ntiles;
@@ -326,13 +342,15 @@ __global__ __launch_bounds__(THREADS, PIPE ? 2 : 3) void conv_implicit_gemm_kern
   if (PIPE) {
     load_a<MODE>(x, cp, rc, 0, ra);
     load_b(wgt, cp.Cout, cp.K, n0, 0, rb);
-    write_tile(ra, lds_a[0]);
-    write_tile(rb, lds_b[0]);
+    write_tile(ra, lds);
+    write_tile(rb, lds + TILE_HALFS);
     __syncthreads();
   }
 
   for (int t = 0; t < nk; ++t) {
     const int cur = PIPE ? (t & 1) : 0;
+    const unsigned short* la = lds + (2 * cur) * TILE_HALFS;
+    const unsigned short* lb = la + TILE_HALFS;
     if (PIPE) {
       // issue next tile's global loads now — they stay in flight under the
       // MFMA phase and are only waited for at the ds_write below
@@ -343,8 +361,8 @@ __global__ __launch_bounds__(THREADS, PIPE ? 2 : 3) void conv_implicit_gemm_kern
     } else {
       load_a<MODE>(x, cp, rc, t * BK, ra);
       load_b(wgt, cp.Cout, cp.K, n0, t * BK, rb);
-      write_tile(ra, lds_a[0]);
-      write_tile(rb, lds_b[0]);
+      write_tile(ra, lds);
+      write_tile(rb, lds + TILE_HALFS);
       __syncthreads();
     }
 #pragma unroll
@@ -353,10 +371,10 @@ __global__ __launch_bounds__(THREADS, PIPE ? 2 : 3) void conv_implicit_gemm_kern
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const unsigned short* pa =
-            lds_a[cur] + (wm + i * 16 + frag_row) * LDS_PITCH + ks + frag_koff;
+            la + (wm + i * 16 + frag_row) * LDS_PITCH + ks + frag_koff;
         afrag[i] = *reinterpret_cast<const short8*>(pa);
         const unsigned short* pb =
-            lds_b[cur] + (wn + i * 16 + frag_row) * LDS_PITCH + ks + frag_koff;
+            lb + (wn + i * 16 + frag_row) * LDS_PITCH + ks + frag_koff;
         bfrag[i] = *reinterpret_cast<const short8*>(pb);
       }
 #pragma unroll
@@ -369,8 +387,8 @@ __global__ __launch_bounds__(THREADS, PIPE ? 2 : 3) void conv_implicit_gemm_kern
     if (PIPE) {
       if (t + 1 < nk) {
         __syncthreads();  // everyone finished reading buf[cur^1] (tile t-1)
-        write_tile(ra, lds_a[cur ^ 1]);
-        write_tile(rb, lds_b[cur ^ 1]);
+        write_tile(ra, lds + (2 * (cur ^ 1)) * TILE_HALFS);
+        write_tile(rb, lds + (2 * (cur ^ 1) + 1) * TILE_HALFS);
         __syncthreads();
       }
     } else {
@@ -381,23 +399,105 @@ __global__ __launch_bounds__(THREADS, PIPE ? 2 : 3) void conv_implicit_gemm_kern
   // epilogue: lane l, reg r -> row (l/16)*4 + r, col l%16 of each 16x16 frag
   const int erow = (lane / 16) * 4;
   const int ecol = lane % 16;
+  if (EPI == EPI_NARROW) {
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < 4; ++i) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int64_t m = m0 + wm + i * 16 + erow + r;
-      if (m >= cp.M) continue;
+      for (int r = 0; r < 4; ++r) {
+        const int64_t m = m0 + wm + i * 16 + erow + r;
+        if (m >= cp.M) continue;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int n = n0 + wn + j * 16 + ecol;
-        if (n >= cp.Cout) continue;
-        float v = acc[i][j][r];
-        if (HAS_BIAS) v += bias[n];
+        for (int j = 0; j < 4; ++j) {
+          const int n = n0 + wn + j * 16 + ecol;
+          if (n >= cp.Cout) continue;
+          float v = acc[i][j][r];
+          if (HAS_BIAS) v += bias[n];
+          if (RELU) v = fmaxf(v, 0.f);
+          *reinterpret_cast<unsigned short*>(out + m * cp.Cout + n) = f_to_bf16(v);
+        }
+      }
+    }
+    return;
+  }
+
+  // ---- wide epilogue.  The simple loop left its last k-step behind a
+  // barrier; the pipelined loop did not, and the staging overwrites both
+  // buffers.
+  if (PIPE) __syncthreads();
+  if (EPI == EPI_WIDE_RES) {
+    // residual tile -> staging, 16 B per lane; rows / columns outside the
+    // tensor stay unread (their staging slots are never stored either)
+#pragma unroll
+    for (int q = 0; q < (BM * BN / 8) / THREADS; ++q) {
+      const int idx = threadIdx.x + q * THREADS;
+      const int row = idx / (BN / 8);
+      const int cc = (idx % (BN / 8)) * 8;
+      const int64_t m = m0 + row;
+      const int n = n0 + cc;
+      uint4 v = make_uint4(0, 0, 0, 0);
+      if (m < cp.M && n < cp.Cout)
+        v = *reinterpret_cast<const uint4*>(res + m * cp.Cout + n);
+      *reinterpret_cast<uint4*>(lds + row * C_PITCH + cc) = v;
+    }
+    __syncthreads();
+  }
+  // every C element has one owner lane: it reads the residual from its
+  // staging slot, adds in fp32 (acc + bias, then + residual), rounds once
+  // and writes the bf16 result back to the same slot
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int col = wn + j * 16 + ecol;
+    const float b = (n0 + col < cp.Cout) ? bias[n0 + col] : 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        unsigned short* slot = lds + (wm + i * 16 + erow + r) * C_PITCH + col;
+        float v = acc[i][j][r] + b;
+        if (EPI == EPI_WIDE_RES) v += bf16_to_f(*slot);
         if (RELU) v = fmaxf(v, 0.f);
-        *reinterpret_cast<unsigned short*>(out + m * cp.Cout + n) = f_to_bf16(v);
+        *slot = f_to_bf16(v);
       }
     }
   }
+  __syncthreads();
+  // ---- C tile out: 16 B per lane, 16 lanes per 256-B row ----
+#pragma unroll
+  for (int q = 0; q < (BM * BN / 8) / THREADS; ++q) {
+    const int idx = threadIdx.x + q * THREADS;
+    const int row = idx / (BN / 8);
+    const int cc = (idx % (BN / 8)) * 8;
+    const int64_t m = m0 + row;
+    const int n = n0 + cc;
+    if (m < cp.M && n < cp.Cout)
+      *reinterpret_cast<uint4*>(out + m * cp.Cout + n) =
+          *reinterpret_cast<const uint4*>(lds + row * C_PITCH + cc);
+  }
+}
+
+template <int MODE, bool RELU, bool HAS_BIAS, bool PIPE, bool SWZ>
+__global__ __launch_bounds__(THREADS, PIPE ? 2 : 3) void conv_implicit_gemm_kernel(
+    const bf16* __restrict__ x, const bf16* __restrict__ wgt,
+    const float* __restrict__ bias, bf16* __restrict__ out, ConvParams cp,
+    int mtiles, int ntiles) {
+  __shared__ __attribute__((aligned(16)))
+  unsigned short lds[(PIPE ? 2 : 1) * 2 * TILE_HALFS];
+  conv_gemm_tile<MODE, RELU, HAS_BIAS, PIPE, SWZ, EPI_NARROW>(
+      x, wgt, bias, nullptr, out, cp, mtiles, ntiles, lds);
+}
+
+// Folded-inference conv forward: out = bf16(relu?(acc + bias [+ res])).
+// Needs Cout % 8 == 0 and 16-byte aligned out / res (checked by the caller).
+template <int MODE, bool RELU, bool HAS_RES, bool PIPE, bool SWZ>
+__global__ __launch_bounds__(THREADS, PIPE ? 2 : 3) void conv_fused_fwd_kernel(
+    const bf16* __restrict__ x, const bf16* __restrict__ wgt,
+    const float* __restrict__ bias, const bf16* __restrict__ res,
+    bf16* __restrict__ out, ConvParams cp, int mtiles, int ntiles) {
+  __shared__ __attribute__((aligned(16)))
+  unsigned short lds[(PIPE ? 2 : 1) * 2 * TILE_HALFS];
+  conv_gemm_tile<MODE, RELU, true, PIPE, SWZ,
+                 HAS_RES ? EPI_WIDE_RES : EPI_WIDE>(
+      x, wgt, bias, res, out, cp, mtiles, ntiles, lds);
 }
 
 // ===========================================================================
@@ -429,8 +529,6 @@ __global__ __launch_bounds__(THREADS, PIPE ? 2 : 3) void conv_implicit_gemm_kern
 // ===========================================================================
 
 enum StatsKind { STATS_BN = 0, STATS_WHITEN4 = 1 };
-
-constexpr int C_PITCH = BN + PAD_HALFS;  // C staging row pitch (halves)
 
 template <int CTRL>
 DEV_INLINE float quad_bcast(float v) {
@@ -1114,6 +1212,80 @@ void mfma_conv2d_fwd(Tensor x, Tensor wgt, Tensor bias, Tensor out,
   };
   if (gemm_fast) pick_rb(std::true_type{});
   else pick_rb(std::false_type{});
+}
+
+// Folded-inference conv fwd: the kernel body, grid and PIPE / SWZ choices of
+// mfma_conv2d_fwd with the wide epilogue,
+//   out = bf16( [relu]( acc + bias[co] [+ float(res)] ) ),
+// fp32 adds in that order and one rounding.  res has out's shape and layout
+// (ignored unless has_res).  The 16-byte epilogue accesses need
+// Cout % 8 == 0 and 16-byte aligned out / res.
+void mfma_conv2d_fwd_fused(Tensor x, Tensor wgt, Tensor bias, Tensor res,
+                           Tensor out, int64_t N, int64_t H, int64_t W,
+                           int64_t Cin, int64_t P, int64_t Q, int64_t Cout,
+                           int64_t KH, int64_t KW, int64_t stride, int64_t pad,
+                           bool relu, bool has_res) {
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 &&
+              wgt.scalar_type() == at::kBFloat16 &&
+              out.scalar_type() == at::kBFloat16 &&
+              bias.scalar_type() == at::kFloat, "mfma_conv2d_fwd_fused: dtypes");
+  TORCH_CHECK(x.is_cuda() && wgt.is_cuda() && bias.is_cuda() && out.is_cuda());
+  TORCH_CHECK(Cout % 8 == 0, "mfma_conv2d_fwd_fused: Cout % 8");
+  TORCH_CHECK(x.numel() == N * H * W * Cin && wgt.numel() == Cout * KH * KW * Cin &&
+              bias.numel() == Cout && out.numel() == N * P * Q * Cout,
+              "mfma_conv2d_fwd_fused: sizes");
+  TORCH_CHECK(P == (H + 2 * pad - KH) / stride + 1 &&
+              Q == (W + 2 * pad - KW) / stride + 1,
+              "mfma_conv2d_fwd_fused: output extent");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0,
+              "mfma_conv2d_fwd_fused: out alignment");
+  if (has_res) {
+    TORCH_CHECK(res.is_cuda() && res.scalar_type() == at::kBFloat16 &&
+                res.numel() == out.numel() &&
+                reinterpret_cast<uintptr_t>(res.data_ptr()) % 16 == 0,
+                "mfma_conv2d_fwd_fused: res");
+  }
+  dwtmm::ConvParams cp{};
+  cp.N = N; cp.H = H; cp.W = W; cp.Cin = Cin;
+  cp.P = P; cp.Q = Q; cp.Cout = Cout;
+  cp.KH = KH; cp.KW = KW; cp.stride = stride; cp.pad = pad;
+  cp.M = N * P * Q;
+  cp.K = KH * KW * Cin;
+  cp.cShift = log2_if_pow2(Cin);
+  const int64_t mt64 = (cp.M + dwtmm::BM - 1) / dwtmm::BM;
+  const int ntiles = (Cout + dwtmm::BN - 1) / dwtmm::BN;
+  TORCH_CHECK(cp.M > 0 && mt64 * ntiles < (int64_t)1 << 31);
+  const int mtiles = (int)mt64;
+  const bool gemm_fast = (KH == 1 && KW == 1 && stride == 1 && pad == 0 &&
+                          Cin % 8 == 0);
+  const bool pipe = gemm_fast && cp.K >= 4 * dwtmm::BK;
+  const bool swz = gemm_fast && ntiles >= 8 && mtiles * ntiles >= 16;
+  auto launch = [&](auto modec, auto reluc, auto resc, auto pipec, auto swzc) {
+    hipLaunchKernelGGL(
+        (dwtmm::conv_fused_fwd_kernel<decltype(modec)::value,
+                                      decltype(reluc)::value,
+                                      decltype(resc)::value,
+                                      decltype(pipec)::value,
+                                      decltype(swzc)::value>),
+        dim3(mtiles * ntiles), dim3(dwtmm::THREADS), 0, dwtmm_stream(),
+        (const c10::BFloat16*)x.data_ptr(), (const c10::BFloat16*)wgt.data_ptr(),
+        bias.data_ptr<float>(),
+        has_res ? (const c10::BFloat16*)res.data_ptr() : nullptr,
+        (c10::BFloat16*)out.data_ptr(), cp, mtiles, ntiles);
+  };
+  using DEN = std::integral_constant<int, dwtmm::A_DENSE>;
+  using CNV = std::integral_constant<int, dwtmm::A_CONV>;
+  auto pick_mode = [&](auto reluc, auto resc) {
+    if (!gemm_fast) { launch(CNV{}, reluc, resc, std::false_type{}, std::false_type{}); return; }
+    if (pipe) { if (swz) launch(DEN{}, reluc, resc, std::true_type{}, std::true_type{});
+                else launch(DEN{}, reluc, resc, std::true_type{}, std::false_type{}); }
+    else { if (swz) launch(DEN{}, reluc, resc, std::false_type{}, std::true_type{});
+           else launch(DEN{}, reluc, resc, std::false_type{}, std::false_type{}); }
+  };
+  if (relu) { if (has_res) pick_mode(std::true_type{}, std::true_type{});
+              else pick_mode(std::true_type{}, std::false_type{}); }
+  else { if (has_res) pick_mode(std::false_type{}, std::true_type{});
+         else pick_mode(std::false_type{}, std::false_type{}); }
 }
 
 

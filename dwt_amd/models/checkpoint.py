@@ -75,6 +75,55 @@ def load_training_state(path: str, model, optimizer=None, scheduler=None,
 
 
 # ---------------------------------------------------------------------------
+# Folded inference model (models/folded.py)
+# ---------------------------------------------------------------------------
+
+FOLDED_FORMAT = "dwt_amd.folded.v1"
+
+
+def save_folded(path: str, folded) -> None:
+    """Write a ``FoldedResNetDWT``: its tensors (named after the source
+    modules), each conv's stride / padding and a small meta dict (``layers``,
+    ``num_classes``, ``branch``, ``whiten_mode``, ``dtype``).  Atomic, like
+    :func:`save_training_state`."""
+    specs = folded.conv_specs()
+    meta = dict(folded.meta)
+    meta.setdefault("layers", list(folded.layers))
+    meta.setdefault("num_classes", folded.num_classes)
+    meta.setdefault("dtype", str(folded.conv1.weight.dtype).replace("torch.", ""))
+    state = {
+        "format": FOLDED_FORMAT,
+        "meta": meta,
+        "geometry": {k: (s, p) for k, (_, _, s, p) in specs.items()},
+        "tensors": {k: v.detach().cpu() for k, v in folded.state_dict().items()},
+    }
+    tmp = path + ".tmp"
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    torch.save(state, tmp)
+    os.replace(tmp, path)
+
+
+def load_folded(path: str, device=None):
+    """Rebuild the ``FoldedResNetDWT`` that :func:`save_folded` wrote; the
+    training model is not needed."""
+    from .folded import FoldedResNetDWT
+    state = torch.load(path, map_location="cpu", weights_only=False)
+    assert isinstance(state, dict) and state.get("format") == FOLDED_FORMAT, \
+        "not a dwt_amd folded checkpoint"
+    t = state["tensors"]
+    if device is not None:
+        t = {k: v.to(device) for k, v in t.items()}
+    convs = {}
+    for name, (stride, padding) in state["geometry"].items():
+        w = t[name + ".weight"]
+        convs[name] = (w.contiguous(memory_format=torch.channels_last),
+                       t[name + ".bias"], int(stride), int(padding))
+    meta = state["meta"]
+    return FoldedResNetDWT(meta["layers"], convs, t["fc_out.weight"],
+                           t["fc_out.bias"], meta)
+
+
+# ---------------------------------------------------------------------------
 # Export to the reference layout
 # ---------------------------------------------------------------------------
 

@@ -9,6 +9,10 @@ accumulate, bf16 out — the v_mfma_f32_16x16x32_bf16 tile kernel.
 ``conv2d_fwd``: NHWC implicit-GEMM convolution forward on the same kernel
 (1x1 degenerates to the dense-GEMM fast path; KxK gathers patches on the
 fly; the channels_last conv weight is consumed as stored).
+
+``conv2d_fused_fwd``: the same conv with the folded-inference epilogue,
+``bf16(relu(conv + bias + residual))`` in one launch (fp32 adds, one
+rounding, 16-byte stores), routed per shape by a measured table.
 """
 from __future__ import annotations
 
@@ -117,6 +121,155 @@ def conv2d_fwd(x: torch.Tensor, weight: torch.Tensor,
         pass  # slow per-element gather path inside the kernel handles it
     _ext().mfma_conv2d_fwd(x, wgt, b32, out, n, h, w, cin, p, q, cout,
                            kh, kw, stride, padding, relu, has_bias)
+    return out
+
+
+# ----------------------------------------------------------------------------
+# Conv forward with the bias / residual / ReLU epilogue (folded inference)
+# ----------------------------------------------------------------------------
+
+# Conv shapes ``(cin, cout, k, stride, has_residual)`` where the library conv
+# with bias plus its elementwise op (in-place relu, or add_relu) measured
+# faster than the fused kernel in the same sitting
+# (profiles/inference_folded.md: N = 256 at 224x224, medians of alternated
+# runs).  `conv2d_fused_fwd(route=True)` sends these to that composition;
+# every other shape stays on the kernel.  The losers are the gather main loop
+# (stem, every 3x3) and three 1x1 shapes with few M-tiles; every other 1x1,
+# every residual join among them, wins by 1.06-2.8x.
+_FUSED_FWD_LIBRARY_SHAPES = frozenset({
+    (3, 64, 7, 2, False),          # stem            0.82 vs 0.74 ms
+    (64, 64, 3, 1, False),         # l1 conv2        0.259 vs 0.231
+    (128, 128, 3, 2, False),       # l2.0 conv2      0.219 vs 0.170
+    (128, 128, 3, 1, False),       # l2 conv2        0.189 vs 0.165
+    (256, 256, 3, 2, False),       # l3.0 conv2      0.289 vs 0.160
+    (256, 256, 3, 1, False),       # l3 conv2        0.274 vs 0.158
+    (512, 512, 3, 2, False),       # l4.0 conv2      0.294 vs 0.201
+    (512, 512, 3, 1, False),       # l4 conv2        0.280 vs 0.195
+    (512, 1024, 1, 2, False),      # l3.0 downsample 0.185 vs 0.165
+    (1024, 512, 1, 1, False),      # l4.0 conv1      0.186 vs 0.159
+    (1024, 2048, 1, 2, False),     # l4.0 downsample 0.207 vs 0.139
+})
+
+
+def fused_fwd_on_kernel(cin: int, cout: int, k: int, stride: int,
+                        has_residual: bool) -> bool:
+    """Whether the routing table keeps this conv shape on the fused kernel."""
+    return (cin, cout, k, stride, bool(has_residual)) \
+        not in _FUSED_FWD_LIBRARY_SHAPES
+
+
+def _storage_range(t: torch.Tensor):
+    lo = t.data_ptr()
+    span = sum((s - 1) * st for s, st in zip(t.shape, t.stride())) + 1
+    return lo, lo + span * t.element_size()
+
+
+def _overlaps(a: torch.Tensor, b: torch.Tensor) -> bool:
+    a0, a1 = _storage_range(a)
+    b0, b1 = _storage_range(b)
+    return a0 < b1 and b0 < a1
+
+
+def _is_nhwc(t: torch.Tensor) -> bool:
+    """Dense NHWC storage (size-1 dims make the torch query ambiguous, so the
+    strides are compared directly)."""
+    n, c, h, w = t.shape
+    want = (h * w * c, 1, w * c, c)
+    return all(s == 1 or st == ws for s, st, ws in zip(t.shape, t.stride(), want))
+
+
+def conv2d_fused_fwd(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
+                     stride: int = 1, padding: int = 0, relu: bool = False,
+                     residual: Optional[torch.Tensor] = None,
+                     out: Optional[torch.Tensor] = None,
+                     route: bool = True) -> torch.Tensor:
+    """NHWC conv forward with the folded-inference epilogue, one launch:
+
+        out = bf16( [relu]( conv(x, weight) + bias [+ residual] ) )
+
+    with the adds in fp32 in that order and one rounding.  x (N, Cin, H, W)
+    and weight (Cout, Cin, KH, KW) channels_last bf16, bias fp32 (Cout,),
+    residual / out (N, Cout, P, Q) channels_last bf16, 16-byte aligned;
+    Cout % 8 == 0; ``out`` (optional, preallocated) aliases neither ``x`` nor
+    ``residual``.  A 3-channel ``x`` is zero-padded to 4 channels here; the
+    weight may come with 3 or (padded once by the caller) 4.
+
+    ``route=True`` (default) sends the shapes of the measured table above to
+    the library conv + elementwise op instead; ``route=False`` and ``out=``
+    always run the kernel.
+    """
+    if x.dim() != 4 or weight.dim() != 4:
+        raise ValueError("conv2d_fused_fwd: x and weight must be 4-D")
+    if x.dtype != torch.bfloat16 or weight.dtype != torch.bfloat16:
+        raise TypeError("conv2d_fused_fwd: x and weight must be bfloat16")
+    n, cin, h, w = x.shape
+    cout, wcin, kh, kw = weight.shape
+    if cout % 8 != 0:
+        raise ValueError(f"conv2d_fused_fwd: Cout % 8 != 0 (Cout = {cout}); "
+                         "the epilogue stores 8 channels per lane")
+    if bias is None or bias.numel() != cout:
+        raise ValueError("conv2d_fused_fwd: bias of Cout elements is required")
+    if wcin not in (cin, 4 if cin == 3 else cin):
+        raise ValueError(f"conv2d_fused_fwd: weight Cin {wcin} vs x Cin {cin}")
+    p = (h + 2 * padding - kh) // stride + 1
+    q = (w + 2 * padding - kw) // stride + 1
+    oshape = (n, cout, p, q)
+    for name, t in (("residual", residual), ("out", out)):
+        if t is None:
+            continue
+        if tuple(t.shape) != oshape:
+            raise ValueError(f"conv2d_fused_fwd: {name}.shape {tuple(t.shape)} "
+                             f"!= output shape {oshape}")
+        if t.dtype != torch.bfloat16 or t.device != x.device:
+            raise TypeError(f"conv2d_fused_fwd: {name} must be bfloat16 on x's device")
+        if not _is_nhwc(t):
+            raise ValueError(f"conv2d_fused_fwd: {name} must be channels_last")
+        if t.data_ptr() % 16 != 0:
+            raise ValueError(f"conv2d_fused_fwd: {name} must be 16-byte aligned")
+    if out is not None:
+        if _overlaps(out, x):
+            raise ValueError("conv2d_fused_fwd: out aliases x")
+        if residual is not None and _overlaps(out, residual):
+            raise ValueError("conv2d_fused_fwd: out aliases residual")
+    if not _is_nhwc(x):
+        x = x.contiguous(memory_format=torch.channels_last)
+    if x.data_ptr() % 16 != 0:      # the A-operand loads are 16 bytes wide
+        x = x.clone(memory_format=torch.preserve_format)
+    b32 = bias.detach()
+    if b32.dtype != torch.float32 or not b32.is_contiguous():
+        b32 = b32.float().contiguous()
+
+    if route and out is None and not fused_fwd_on_kernel(
+            cin, cout, kh, stride, residual is not None):
+        from . import functional as Fdwt
+        wl = weight[:, :cin] if wcin != cin else weight
+        y = F.conv2d(x, wl, b32.to(torch.bfloat16), stride, padding)
+        if residual is not None:
+            return Fdwt.add_relu(y, residual) if relu else y + residual
+        return y.relu_() if relu else y
+
+    if cin == 3:
+        # stem: zero-pad to 4 channels so the kernel's paired-pixel 16-B
+        # path applies (NHWC C=4 chunks)
+        x4 = torch.empty(n, 4, h, w, device=x.device, dtype=x.dtype,
+                         memory_format=torch.channels_last)
+        x4[:, 3] = 0
+        x4[:, :3] = x
+        x, cin = x4, 4
+        if wcin == 3:
+            w4 = weight.new_zeros(cout, 4, kh, kw)
+            w4[:, :3] = weight.detach()
+            weight = w4
+    wgt = weight.detach()
+    if not _is_nhwc(wgt):
+        wgt = wgt.contiguous(memory_format=torch.channels_last)
+    if out is None:
+        out = torch.empty(oshape, device=x.device, dtype=torch.bfloat16,
+                          memory_format=torch.channels_last)
+    has_res = residual is not None
+    _ext().mfma_conv2d_fwd_fused(x, wgt, b32, residual if has_res else out, out,
+                                 n, h, w, cin, p, q, cout, kh, kw, stride,
+                                 padding, relu, has_res)
     return out
 
 

@@ -67,6 +67,14 @@ def build_args(argv=None):
                              "cross-rank synced batch stats")
     parser.add_argument('--stats_passes', type=int, default=10,
                         help='target-stats re-estimation passes before final test')
+    parser.add_argument('--folded_eval', action='store_true',
+                        help='every test() of the run folds the current '
+                             'target-branch norm sites into the convs and '
+                             'evaluates that model (conv + bias [+ identity] '
+                             '[+ ReLU], one launch per conv)')
+    parser.add_argument('--export_folded', type=str, default='',
+                        help='write the folded inference checkpoint here '
+                             'after the final statistics pass')
     on_device = parser.add_mutually_exclusive_group()
     on_device.add_argument('--gpu_augment', action='store_true',
                            help='build the duplicate MEC target view on-device '
