@@ -120,10 +120,10 @@ def stats_mode(args):
         def stats_fn():
             acc = torch.zeros(nacc, device=dev, dtype=torch.float32)
             if kind == "bn":
-                ext.bn_stats_cl(out, acc, mean, istd, var_unb, cout, mp, 1e-5,
-                                parts)
+                ext.bn_stats_partial_cl(out, acc, cout, mp, parts)
             else:
-                ext.whiten_stats_cl(out, acc, mean, cov, g, cout, mp, parts)
+                ext.whiten_stats_partial_cl(out, acc, g, cout, mp, parts)
+            final(acc)
 
         def old_fn():
             return conv2d_fwd(x, wt)

@@ -6,6 +6,14 @@ register-blocked fast path covers group sizes {2, 4, 8}; 8 < g <= 32 runs
 the generic LDS-tiled NCHW kernels (every group size the reference models
 can construct); fp32/bf16 inputs; anything else falls back to the torch
 implementation (warned once).
+
+Every site stacks its domain branches: the launchers of both layouts take the
+whole (parts*B, ...) batch, statistics buffers laid out [parts, ...] and
+``parts``, so a pass is a two-way fork on the layout and nothing here loops
+over branches but the running-buffer EMA and the stacking of running buffers
+in eval.  Batch statistics are taken in one place per Function: raw sums
+(handed over by the producing conv, or a partial launch) -> all-reduce when
+``stats_sync`` spans ranks -> finalize.
 """
 from __future__ import annotations
 
@@ -13,6 +21,7 @@ import warnings
 import torch
 
 from . import dispatch
+from ..ops.functional import _dist_world
 
 _GEN_G_MAX = 32  # register-blocked kernels cover g in {2,4,8};
                  # 8 < g <= 32 runs the LDS-tiled generic NCHW kernels
@@ -88,14 +97,6 @@ def _warn_once(key, msg):
         warnings.warn(msg)
 
 
-def _sync_world():
-    """World size for cross-rank ('sync') batch statistics."""
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized():
-        return dist, dist.get_world_size()
-    return None, 1
-
-
 def _allreduce(t):
     import torch.distributed as dist
     dist.all_reduce(t)
@@ -125,11 +126,12 @@ def _usable_stats_acc(acc, x, layout, training, numel):
 
 class _HipWhitenMulti(torch.autograd.Function):
     """All per-branch statistics are STACKED ([parts*C] means, [parts*G, g, g]
-    covariances/W) so the channels_last path runs ONE launch per pass across
-    all domain branches (grid.y = branch — late-layer sites are launch-bound
-    otherwise, profiles/norm_bench.md); the matrix-function kernels always
-    see the stacked group axis.  The NCHW path loops branches over contiguous
-    slices of the same stacked tensors."""
+    covariances/W) and every pass is one launcher call on the whole batch,
+    in either layout.  The channels_last launchers run ONE launch per pass
+    across all domain branches (grid.y = branch — late-layer sites are
+    launch-bound otherwise, profiles/norm_bench.md); the NCHW launchers
+    launch the branches one after another on offsets into the same stacked
+    tensors; the matrix-function kernels always see the stacked group axis."""
 
     @staticmethod
     def forward(ctx, x, gamma, beta, running_means, running_vars, cfg,
@@ -161,47 +163,27 @@ class _HipWhitenMulti(torch.autograd.Function):
 
         has_affine, gflat, bflat = _flat_affine(gamma, beta, c, x)
 
-        stats_sync = cfg.get("stats_sync", False) and use_batch
-        world = 1
-        if stats_sync:
-            _, world = _sync_world()
+        # world > 1 only with stats_sync: cross-rank (SyncBN-style) statistics
+        world = _dist_world()[1] if cfg.get("stats_sync") and use_batch else 1
         ctx_count = m_count * world  # global positions per branch
 
         out = torch.empty_like(x)
         if use_batch:
+            # raw sums (from the producing conv's epilogue, or a partial pass
+            # here) -> all-reduce -> finalize over the global batch
             acc = _usable_stats_acc(stats_acc, x, layout, training,
                                     ng_all * (g + g * g))
-            pre = acc is not None
-            if not pre:
+            if acc is None:
                 acc = torch.zeros(ng_all * (g + g * g), device=dev, dtype=torch.float32)
-            mean = torch.empty(parts * c, device=dev, dtype=torch.float32)
-            cov = torch.empty(ng_all, g, g, device=dev, dtype=torch.float32)
-            if pre:
-                # raw sums came from the producing conv's epilogue
-                if stats_sync and world > 1:
-                    _allreduce(acc)
-                ext.whiten_stats_final(acc, mean, cov, g, ng_all, ctx_count)
-            elif stats_sync:
-                # split pass: local raw sums -> all-reduce -> finalize over
-                # the GLOBAL batch (SyncBN-style cross-rank statistics)
                 if layout == "cl":
                     ext.whiten_stats_partial_cl(x, acc, g, c, m_count, parts)
                 else:
-                    for p in range(parts):
-                        ext.whiten_stats_partial(
-                            x[p * b:(p + 1) * b],
-                            acc[p * n_groups * (g + g * g):(p + 1) * n_groups * (g + g * g)], g)
-                if world > 1:
-                    _allreduce(acc)
-                ext.whiten_stats_final(acc, mean, cov, g, ng_all, ctx_count)
-            elif layout == "cl":
-                ext.whiten_stats_cl(x, acc, mean, cov, g, c, m_count, parts)
-            else:
-                for p in range(parts):
-                    ext.whiten_stats(x[p * b:(p + 1) * b],
-                                     acc[p * n_groups * (g + g * g):(p + 1) * n_groups * (g + g * g)],
-                                     mean[p * c:(p + 1) * c],
-                                     cov[p * n_groups:(p + 1) * n_groups], g)
+                    ext.whiten_stats_partial(x, acc, g, parts)
+            if world > 1:
+                _allreduce(acc)
+            mean = torch.empty(parts * c, device=dev, dtype=torch.float32)
+            cov = torch.empty(ng_all, g, g, device=dev, dtype=torch.float32)
+            ext.whiten_stats_final(acc, mean, cov, g, ng_all, ctx_count)
         else:
             mean = torch.stack([_f32c(running_means[p]).reshape(c)
                                 for p in range(parts)]).reshape(-1).contiguous()
@@ -228,11 +210,8 @@ class _HipWhitenMulti(torch.autograd.Function):
             ext.whiten_apply_cl(x, mean, wmat, gflat, bflat, out, g, c,
                                 m_count, relu, has_affine, parts)
         else:
-            for p in range(parts):
-                ext.whiten_apply(x[p * b:(p + 1) * b], mean[p * c:(p + 1) * c],
-                                 wmat[p * n_groups:(p + 1) * n_groups], gflat,
-                                 bflat, out[p * b:(p + 1) * b], g, relu,
-                                 has_affine)
+            ext.whiten_apply(x, mean, wmat, gflat, bflat, out, g, relu,
+                             has_affine, parts)
 
         if training and track and running_means is not None:
             with torch.no_grad():
@@ -276,10 +255,8 @@ class _HipWhitenMulti(torch.autograd.Function):
         use_batch = training or not track
         g = ctx.g
         x, gamma, out = ctx.saved_tensors
-        n, c, h, w = x.shape
-        b = n // parts
-        n_groups = c // g
-        ng_all = parts * n_groups
+        c = x.shape[1]
+        ng_all = parts * (c // g)
         dev = x.device
         layout = ctx.layout
         if layout == "cl":
@@ -311,20 +288,16 @@ class _HipWhitenMulti(torch.autograd.Function):
                                      dW, dgb.reshape(-1), g, c, m_local,
                                      relu, ctx.has_affine, parts)
         else:
-            for p in range(parts):
-                sl = slice(p * b, (p + 1) * b)
-                ext.whiten_bwd_reduce(x[sl], dout[sl], out[sl],
-                                      mean[p * c:(p + 1) * c],
-                                      wmat[p * n_groups:(p + 1) * n_groups],
-                                      ctx.gflat, dW[p * n_groups:(p + 1) * n_groups],
-                                      dgb[p].reshape(-1), g, relu, ctx.has_affine)
+            ext.whiten_bwd_reduce(x, dout, out, mean, wmat, ctx.gflat, dW,
+                                  dgb.reshape(-1), g, relu, ctx.has_affine,
+                                  parts)
 
         if use_batch:
             gdb = (ctx.gflat.float().unsqueeze(0) * dgb[:, 1]) if ctx.has_affine \
                 else dgb[:, 1]
             gdb = gdb.reshape(-1).contiguous()
             dW_in = dW
-            if getattr(ctx, "sync_world", 1) > 1:
+            if ctx.sync_world > 1:
                 # global-batch statistics: the matrix-function backward sees
                 # the cross-rank sums (dgamma/dbeta stay LOCAL — the DP
                 # gradient all-reduce handles parameter grads)
@@ -349,15 +322,8 @@ class _HipWhitenMulti(torch.autograd.Function):
                                     S, corr, dx, g, c, m_local, relu,
                                     ctx.has_affine, use_batch, parts)
         else:
-            for p in range(parts):
-                sl = slice(p * b, (p + 1) * b)
-                Sp = S[p * n_groups:(p + 1) * n_groups] if use_batch else S
-                cp = corr[p * c:(p + 1) * c] if use_batch else corr
-                ext.whiten_bwd_apply(x[sl], dout[sl], out[sl],
-                                     mean[p * c:(p + 1) * c],
-                                     wmat[p * n_groups:(p + 1) * n_groups],
-                                     ctx.gflat, Sp, cp, dx[sl], g, relu,
-                                     ctx.has_affine, use_batch)
+            ext.whiten_bwd_apply(x, dout, out, mean, wmat, ctx.gflat, S, corr,
+                                 dx, g, relu, ctx.has_affine, use_batch, parts)
 
         if ctx.has_affine:
             dgamma = dgb[:, 0].sum(0).reshape(gamma.shape).to(gamma.dtype)
@@ -365,35 +331,6 @@ class _HipWhitenMulti(torch.autograd.Function):
         else:
             dgamma = dbeta = None
         return dx, gid, dgamma, dbeta
-
-
-class _HipWhitenJoin(torch.autograd.Function):
-    """y = relu(whiten(x) + identity) with the join fused into the apply
-    pass (forward) and into the reduce pass (backward); channels_last only.
-
-    Returns TWO outputs aliasing one buffer, one per consumer of a block
-    output (the next block's conv1 and its identity).  Backward then gets
-    the two gradients un-summed (either may be None) and adds them inside
-    the join reduce kernel — autograd never runs its accumulation kernel."""
-
-    @staticmethod
-    def forward(ctx, x, identity, gamma, beta, running_means, running_vars,
-                cfg):
-        ctx.set_materialize_grads(False)
-        res = identity.detach()  # channels_last: join_supported checked it
-        y = _HipWhitenMulti.forward(ctx, x, gamma, beta, running_means,
-                                    running_vars, cfg, res=res)
-        return y, y.view_as(y)
-
-    @staticmethod
-    def backward(ctx, ga, gb):
-        if ga is None and gb is None:
-            return (None,) * 7
-        if ga is None:
-            ga, gb = gb, None
-        dx, gid, dgamma, dbeta = _HipWhitenMulti.run_backward(
-            ctx, ga, gb, join=True)
-        return dx, gid, dgamma, dbeta, None, None, None
 
 
 def join_supported(kind, x, identity, cfg):
@@ -439,7 +376,7 @@ class _HipBatchNormMulti(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, running_means, running_vars, cfg,
                 res=None):
-        # res: as in _HipWhitenMulti.forward (passed by _HipBatchNormJoin)
+        # res: as in _HipWhitenMulti.forward
         ext = _ext()
         stats_acc = cfg.pop("stats_acc", None)  # as in _HipWhitenMulti
         parts = cfg["parts"]
@@ -455,53 +392,32 @@ class _HipBatchNormMulti(torch.autograd.Function):
             x = x.contiguous()
         n = x.shape[0]
         assert n % parts == 0,             f"batch {n} not divisible by {parts} domain branches"
-        b = n // parts
         dev = x.device
         cnt = (x.numel() // parts) // c
 
         has_affine, gflat, bflat = _flat_affine(gamma, beta, c, x)
 
-        stats_sync = cfg.get("stats_sync", False) and use_batch
-        world = 1
-        if stats_sync:
-            _, world = _sync_world()
+        # as in _HipWhitenMulti.forward
+        world = _dist_world()[1] if cfg.get("stats_sync") and use_batch else 1
         cnt_total = cnt * world
 
         out = torch.empty_like(x)
         if use_batch:
             acc = _usable_stats_acc(stats_acc, x, layout, training,
                                     parts * 2 * c)
-            pre = acc is not None
-            if not pre:
+            if acc is None:
                 acc = torch.zeros(parts * 2 * c, device=dev, dtype=torch.float32)
-            mean = torch.empty(parts * c, device=dev, dtype=torch.float32)
-            istd = torch.empty(parts * c, device=dev, dtype=torch.float32)
-            var_unb = torch.empty(parts * c, device=dev, dtype=torch.float32)
-            if pre:
-                if stats_sync and world > 1:
-                    _allreduce(acc)
-                ext.bn_stats_final(acc, mean, istd, var_unb, c, parts,
-                                   cnt_total, eps)
-            elif stats_sync:
                 if layout == "cl":
                     ext.bn_stats_partial_cl(x, acc, c, cnt, parts)
                 else:
-                    for p in range(parts):
-                        ext.bn_stats_partial(x[p * b:(p + 1) * b],
-                                             acc[p * 2 * c:(p + 1) * 2 * c])
-                if world > 1:
-                    _allreduce(acc)
-                ext.bn_stats_final(acc, mean, istd, var_unb, c, parts,
-                                   cnt_total, eps)
-            elif layout == "cl":
-                ext.bn_stats_cl(x, acc, mean, istd, var_unb, c, cnt, eps, parts)
-            else:
-                for p in range(parts):
-                    ext.bn_stats(x[p * b:(p + 1) * b],
-                                 acc[p * 2 * c:(p + 1) * 2 * c],
-                                 mean[p * c:(p + 1) * c],
-                                 istd[p * c:(p + 1) * c],
-                                 var_unb[p * c:(p + 1) * c], eps)
+                    ext.bn_stats_partial(x, acc, parts)
+            if world > 1:
+                _allreduce(acc)
+            mean = torch.empty(parts * c, device=dev, dtype=torch.float32)
+            istd = torch.empty(parts * c, device=dev, dtype=torch.float32)
+            var_unb = torch.empty(parts * c, device=dev, dtype=torch.float32)
+            ext.bn_stats_final(acc, mean, istd, var_unb, c, parts, cnt_total,
+                               eps)
             if training and track and running_means is not None:
                 with torch.no_grad():
                     for p in range(parts):
@@ -523,10 +439,8 @@ class _HipBatchNormMulti(torch.autograd.Function):
             ext.bn_apply_cl(x, mean, istd, gflat, bflat, out, c, cnt, relu,
                             has_affine, parts)
         else:
-            for p in range(parts):
-                ext.bn_apply(x[p * b:(p + 1) * b], mean[p * c:(p + 1) * c],
-                             istd[p * c:(p + 1) * c], gflat, bflat,
-                             out[p * b:(p + 1) * b], relu, has_affine)
+            ext.bn_apply(x, mean, istd, gflat, bflat, out, relu, has_affine,
+                         parts)
 
         ctx.cfg = cfg
         ctx.layout = layout
@@ -556,8 +470,7 @@ class _HipBatchNormMulti(torch.autograd.Function):
         cfg = ctx.cfg
         parts, relu = cfg["parts"], cfg["relu"]
         x, gamma, out = ctx.saved_tensors
-        n, c = x.shape[0], x.shape[1]
-        b = n // parts
+        c = x.shape[1]
         dev = x.device
         layout = ctx.layout
         if layout == "cl" and x.dim() == 4:
@@ -568,45 +481,37 @@ class _HipBatchNormMulti(torch.autograd.Function):
 
         sums = torch.zeros(parts, 2, c, device=dev, dtype=torch.float32)
         dx = torch.empty_like(x)
-        cnt_total = getattr(ctx, "cnt_total", ctx.cnt)
         gid = None
-        if layout == "cl":
-            if join:
-                if gb is not None:
-                    gb = gb.contiguous(memory_format=torch.channels_last)
-                gid = torch.empty_like(x)
-                ext.bn_join_bwd_reduce_cl(x, out, dout, gb, mean, istd, gid,
-                                          sums.reshape(-1), c, ctx.cnt, parts)
-                dout, relu = gid, False
-            else:
-                ext.bn_bwd_reduce_cl(x, dout, mean, istd, ctx.gflat, ctx.bflat,
-                                     sums.reshape(-1), c, ctx.cnt, relu,
-                                     ctx.has_affine, parts)
-            apply_sums = sums
-            if getattr(ctx, "sync_world", 1) > 1:
-                apply_sums = _allreduce(sums.clone())
-            ext.bn_bwd_apply_cl(x, dout, mean, istd, ctx.gflat, ctx.bflat,
-                                apply_sums.reshape(-1), dx, c, ctx.cnt, relu,
-                                ctx.has_affine, ctx.use_batch, parts,
-                                cnt_total)
+        if join:
+            assert layout == "cl"
+            if gb is not None:
+                gb = gb.contiguous(memory_format=torch.channels_last)
+            gid = torch.empty_like(x)
+            ext.bn_join_bwd_reduce_cl(x, out, dout, gb, mean, istd, gid,
+                                      sums.reshape(-1), c, ctx.cnt, parts)
+            dout, relu = gid, False
+        elif layout == "cl":
+            ext.bn_bwd_reduce_cl(x, dout, mean, istd, ctx.gflat, ctx.bflat,
+                                 sums.reshape(-1), c, ctx.cnt, relu,
+                                 ctx.has_affine, parts)
         else:
-            for p in range(parts):
-                sl = slice(p * b, (p + 1) * b)
-                ext.bn_bwd_reduce(x[sl], dout[sl], out[sl],
-                                  mean[p * c:(p + 1) * c],
-                                  istd[p * c:(p + 1) * c],
-                                  sums[p].reshape(-1), relu)
-            apply_sums = sums
-            if getattr(ctx, "sync_world", 1) > 1:
-                apply_sums = _allreduce(sums.clone())
-            for p in range(parts):
-                sl = slice(p * b, (p + 1) * b)
-                ext.bn_bwd_apply(x[sl], dout[sl], out[sl],
-                                 mean[p * c:(p + 1) * c],
-                                 istd[p * c:(p + 1) * c],
-                                 ctx.gflat, apply_sums[p].reshape(-1), dx[sl],
-                                 relu, ctx.has_affine, ctx.use_batch,
-                                 cnt_total)
+            ext.bn_bwd_reduce(x, dout, out, mean, istd, sums.reshape(-1), relu,
+                              parts)
+
+        # global-batch statistics: the apply pass sees the cross-rank sums
+        # (dgamma / dbeta below stay local, as in _HipWhitenMulti)
+        apply_sums = sums.reshape(-1)
+        if ctx.sync_world > 1:
+            apply_sums = _allreduce(apply_sums.clone())
+        if layout == "cl":
+            ext.bn_bwd_apply_cl(x, dout, mean, istd, ctx.gflat, ctx.bflat,
+                                apply_sums, dx, c, ctx.cnt, relu,
+                                ctx.has_affine, ctx.use_batch, parts,
+                                ctx.cnt_total)
+        else:
+            ext.bn_bwd_apply(x, dout, out, mean, istd, ctx.gflat, apply_sums,
+                             dx, relu, ctx.has_affine, ctx.use_batch,
+                             ctx.cnt_total, parts)
 
         if ctx.has_affine:
             # dgamma = sum dy * xhat ; dbeta = sum dy  (sums[:,1] is dy*xhat)
@@ -617,27 +522,39 @@ class _HipBatchNormMulti(torch.autograd.Function):
         return dx, gid, dgamma, dbeta
 
 
-class _HipBatchNormJoin(torch.autograd.Function):
-    """y = relu(bn(x) + identity); see _HipWhitenJoin."""
+def _join_function(name, site):
+    """y = relu(site(x) + identity) with the join fused into the apply pass
+    (forward) and into the reduce pass (backward); channels_last only.
 
-    @staticmethod
+    Returns TWO outputs aliasing one buffer, one per consumer of a block
+    output (the next block's conv1 and its identity).  Backward then gets
+    the two gradients un-summed (either may be None) and adds them inside
+    the join reduce kernel — autograd never runs its accumulation kernel."""
+
     def forward(ctx, x, identity, gamma, beta, running_means, running_vars,
                 cfg):
         ctx.set_materialize_grads(False)
         res = identity.detach()  # channels_last: join_supported checked it
-        y = _HipBatchNormMulti.forward(ctx, x, gamma, beta, running_means,
-                                       running_vars, cfg, res=res)
+        y = site.forward(ctx, x, gamma, beta, running_means, running_vars,
+                         cfg, res=res)
         return y, y.view_as(y)
 
-    @staticmethod
     def backward(ctx, ga, gb):
         if ga is None and gb is None:
             return (None,) * 7
         if ga is None:
             ga, gb = gb, None
-        dx, gid, dgamma, dbeta = _HipBatchNormMulti.run_backward(
-            ctx, ga, gb, join=True)
+        dx, gid, dgamma, dbeta = site.run_backward(ctx, ga, gb, join=True)
         return dx, gid, dgamma, dbeta, None, None, None
+
+    return type(name, (torch.autograd.Function,),
+                {"__doc__": _join_function.__doc__,
+                 "forward": staticmethod(forward),
+                 "backward": staticmethod(backward)})
+
+
+_HipWhitenJoin = _join_function("_HipWhitenJoin", _HipWhitenMulti)
+_HipBatchNormJoin = _join_function("_HipBatchNormJoin", _HipBatchNormMulti)
 
 
 def batch_norm_multi(x, gamma, beta, running_means, running_vars, cfg):

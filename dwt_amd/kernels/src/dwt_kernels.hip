@@ -2444,60 +2444,363 @@ inline int64_t reduce_blocks(int64_t work_per_group, int threads, int vec,
     }                                                                          \
   }()
 
-template <typename scalar_t>
-bool can_vectorize(const Tensor& t, int64_t HW) {
-  constexpr int VW = dwt::VecTraits<scalar_t>::W;
-  if (HW % VW != 0) return false;
-  return (reinterpret_cast<uintptr_t>(t.data_ptr()) % 16) == 0;
+// null for an operand the kernels treat as optional (gamma / beta without an
+// affine, the join's second consumer)
+template <typename T>
+inline T* opt_ptr(const Tensor& t, bool present) {
+  return present ? t.data_ptr<T>() : nullptr;
+}
+template <typename T>
+inline T* opt_ptr(const c10::optional<Tensor>& t) {
+  return t.has_value() ? t->data_ptr<T>() : nullptr;
 }
 
-// ---------------------------- whitening ----------------------------------
+// ------------------ statistics finalize (either layout) ------------------
 
+// count = number of positions the accumulators were summed over (the GLOBAL
+// batch count in sync-stats mode — acc is all-reduced between the partial
+// pass and this finalize)
 void whiten_stats_final(Tensor acc, Tensor mean, Tensor cov, int64_t g,
-                        int64_t n_groups, int64_t count);  // defined below
+                        int64_t n_groups, int64_t count) {
+  const int fin_threads = std::min<int64_t>(g * g, 1024);
+  hipLaunchKernelGGL(dwt::whiten_stats_final_kernel, dim3(n_groups),
+                     dim3(fin_threads), 0, cur_stream(), acc.data_ptr<float>(),
+                     mean.data_ptr<float>(), cov.data_ptr<float>(),
+                     (int)n_groups, (int)g, 1.0f / (float)count);
+}
 
-void whiten_stats_partial(Tensor x, Tensor acc, int64_t g) {
-  const int B = x.size(0), C = x.size(1);
-  const int64_t HW = x.size(2) * x.size(3);
-  const int64_t M = (int64_t)B * HW;
-  const int n_groups = C / g;
+void bn_stats_final(Tensor acc, Tensor mean, Tensor istd, Tensor var_unb,
+                    int64_t C, int64_t parts, int64_t count, double eps) {
+  const float unb = count > 1 ? (float)count / (float)(count - 1) : 1.f;
+  const int total = parts * C;
+  hipLaunchKernelGGL(dwt::bn_stats_final_kernel, dim3((total + 255) / 256),
+                     dim3(256), 0, cur_stream(), acc.data_ptr<float>(),
+                     mean.data_ptr<float>(), istd.data_ptr<float>(),
+                     var_unb.data_ptr<float>(), total, (int)C,
+                     1.0f / (float)count, unb, (float)eps);
+}
+
+// ------------------------- NCHW launchers --------------------------------
+// One call serves all `parts` domain branches, as in the NHWC launchers: x /
+// dout / out / dx are the full contiguous (parts*B, C, H, W) tensors (BN also
+// (parts*B, C)), and acc, mean, cov / W / istd, dWacc, dgb / sums, S, corr
+// are stacked [parts, ...].  The NCHW kernels see one branch, so the branches
+// are launched one after another on pointers offset by the per-branch
+// extents; B, M and the vector/scalar choice are per branch.
+struct NchwParts {
+  const char* name;
+  int64_t parts, HW, M, numel;  // per branch: M positions, numel elements
+  int B, C;
+
+  // streamed: the tensors read or written alongside x
+  NchwParts(const char* name_, const Tensor& x, int64_t parts_,
+            std::initializer_list<Tensor> streamed = {})
+      : name(name_), parts(parts_) {
+    TORCH_CHECK(x.is_contiguous() && (x.dim() == 4 || x.dim() == 2), name,
+                ": x must be contiguous (N, C, H, W) or (N, C)");
+    TORCH_CHECK(parts > 0 && x.size(0) % parts == 0, name, ": batch ",
+                x.size(0), " does not split into ", parts, " branches");
+    for (const Tensor& t : streamed)
+      TORCH_CHECK(t.scalar_type() == x.scalar_type() &&
+                      t.numel() == x.numel() && t.is_contiguous(),
+                  name, ": dtype, size or layout mismatch with x");
+    B = x.size(0) / parts;
+    C = x.size(1);
+    HW = x.dim() == 4 ? x.size(2) * x.size(3) : 1;
+    M = (int64_t)B * HW;
+    numel = M * C;
+  }
+  int groups(int64_t g) const {
+    TORCH_CHECK(g > 0 && C % g == 0, name, ": group size ", g,
+                " does not divide C = ", C);
+    return C / g;
+  }
+  // each operand holds `per` elements for every branch
+  void stacked(std::initializer_list<std::pair<Tensor, int64_t>> ops) const {
+    for (const auto& [t, per] : ops)
+      TORCH_CHECK(t.numel() == parts * per, name, ": a stacked operand has ",
+                  t.numel(), " elements, expected ", parts * per);
+  }
+};
+
+// Branch p of a streamed tensor, at(t), or of a float operand that holds
+// `per` elements for every branch, at(t, per); per = 0 for one that is not
+// stacked (the empty S / corr in eval).
+template <typename T>
+struct NchwBranch {
+  const NchwParts& d;
+  int64_t p;
+  T* operator()(const Tensor& t) const { return t.data_ptr<T>() + p * d.numel; }
+  float* operator()(const Tensor& t, int64_t per) const {
+    return t.data_ptr<float>() + p * per;
+  }
+};
+
+// a (sample, channel) plane of HW positions at p admits 16-byte accesses
+template <typename T>
+bool can_vectorize(const T* p, int64_t HW) {
+  return HW % dwt::VecTraits<T>::W == 0 &&
+         reinterpret_cast<uintptr_t>(p) % 16 == 0;
+}
+
+// f(bool_constant VECTOR): the 16-byte form of an NCHW kernel or its scalar one
+template <typename F>
+inline void vec_launch(bool vec, F&& f) {
+  if (vec) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+// The NCHW whitening kernels: f(integral_constant G, bool_constant VECTOR)
+// launches the register-blocked form for g in {2, 4, 8}, gen() the LDS-tiled
+// generic form for 8 < g <= 32.
+template <typename F, typename Gen>
+inline void whiten_nchw_launch(const char* name, int64_t g, bool vec, F&& f,
+                               Gen&& gen) {
+  auto blocked = [&](auto gconst) {
+    vec_launch(vec, [&](auto vconst) { f(gconst, vconst); });
+  };
+  switch (g) {
+    case 2: blocked(std::integral_constant<int, 2>{}); break;
+    case 4: blocked(std::integral_constant<int, 4>{}); break;
+    case 8: blocked(std::integral_constant<int, 8>{}); break;
+    default:
+      TORCH_CHECK(g <= 32, name, ": unsupported group size ", g);
+      gen();
+  }
+}
+
+// Grids of the 256-thread NCHW kernels, rows = channels or groups: a reduction
+// over a row's M positions, and an elementwise pass over one (sample, row)
+// plane of HW positions per (y, z) with `vw` positions per thread
+inline dim3 nchw_reduce_grid(int64_t M, int per_block, int vw, int rows) {
+  return dim3(reduce_blocks(M, per_block, vw, rows), rows);
+}
+inline dim3 nchw_elem_grid(int64_t HW, int vw, int B, int rows) {
+  return dim3((HW + (int64_t)256 * vw - 1) / ((int64_t)256 * vw), B, rows);
+}
+
+void whiten_stats_partial(Tensor x, Tensor acc, int64_t g, int64_t parts) {
+  const NchwParts d("whiten_stats", x, parts);
+  const int n_groups = d.groups(g);
+  const int64_t n_acc = n_groups * (g + g * g);
+  d.stacked({{acc, n_acc}});
   DISPATCH_FT(x, "whiten_stats", [&] {
     constexpr int VW = dwt::VecTraits<scalar_t>::W;
-    const bool vec = g <= 4 && can_vectorize<scalar_t>(x, HW) && (M % VW == 0);
-    const int threads = 256;
-    dim3 grid(reduce_blocks(M, threads, vec ? VW : 1, n_groups), n_groups);
-    auto launch = [&](auto gconst, auto vconst) {
-      constexpr int G = decltype(gconst)::value;
-      constexpr bool V = decltype(vconst)::value;
-      hipLaunchKernelGGL((dwt::whiten_stats_partial_kernel<scalar_t, G, V>), grid,
-                         dim3(threads), 0, cur_stream(),
-                         x.data_ptr<scalar_t>(), acc.data_ptr<float>(), B, C, HW, M);
-    };
-    auto pick_v = [&](auto gconst) {
-      if (vec) launch(gconst, std::true_type{});
-      else launch(gconst, std::false_type{});
-    };
-    switch (g) {
-      case 2: pick_v(std::integral_constant<int, 2>{}); break;
-      case 4: pick_v(std::integral_constant<int, 4>{}); break;
-      case 8: pick_v(std::integral_constant<int, 8>{}); break;
-      default: {
-        TORCH_CHECK(g <= 32, "whiten_stats: unsupported group size ", g);
-        const int64_t mb = reduce_blocks(M, 64, 1, n_groups);
+    for (int64_t p = 0; p < parts; ++p) {
+      const NchwBranch<scalar_t> at{d, p};
+      const bool vec = g <= 4 && can_vectorize(at(x), d.HW) && d.M % VW == 0;
+      whiten_nchw_launch(d.name, g, vec, [&](auto gconst, auto vconst) {
+        constexpr int G = decltype(gconst)::value;
+        constexpr bool V = decltype(vconst)::value;
+        hipLaunchKernelGGL((dwt::whiten_stats_partial_kernel<scalar_t, G, V>),
+                           nchw_reduce_grid(d.M, 256, V ? VW : 1, n_groups),
+                           dim3(256), 0, cur_stream(), at(x), at(acc, n_acc),
+                           d.B, d.C, d.HW, d.M);
+      }, [&] {
         hipLaunchKernelGGL((dwt::whiten_stats_gen_kernel<scalar_t>),
-                           dim3(mb, n_groups), dim3(256), 0, cur_stream(),
-                           x.data_ptr<scalar_t>(), acc.data_ptr<float>(),
-                           (int)g, C, HW, M);
-      }
+                           nchw_reduce_grid(d.M, 64, 1, n_groups), dim3(256), 0,
+                           cur_stream(), at(x), at(acc, n_acc), (int)g, d.C,
+                           d.HW, d.M);
+      });
     }
   });
 }
 
-void whiten_stats(Tensor x, Tensor acc, Tensor mean, Tensor cov, int64_t g) {
-  whiten_stats_partial(x, acc, g);
-  const int C = x.size(1);
-  const int64_t M = (int64_t)x.size(0) * x.size(2) * x.size(3);
-  whiten_stats_final(acc, mean, cov, g, C / g, M);
+void whiten_apply(Tensor x, Tensor mean, Tensor W, Tensor gamma, Tensor beta,
+                  Tensor out, int64_t g, bool relu, bool has_affine,
+                  int64_t parts) {
+  const NchwParts d("whiten_apply", x, parts, {out});
+  const int n_groups = d.groups(g);
+  const int64_t n_w = n_groups * g * g;
+  d.stacked({{mean, d.C}, {W, n_w}});
+  DISPATCH_FT(x, "whiten_apply", [&] {
+    constexpr int VW = dwt::VecTraits<scalar_t>::W;
+    const scalar_t* gp = opt_ptr<scalar_t>(gamma, has_affine);
+    const scalar_t* bp = opt_ptr<scalar_t>(beta, has_affine);
+    for (int64_t p = 0; p < parts; ++p) {
+      const NchwBranch<scalar_t> at{d, p};
+      const bool vec = can_vectorize(at(x), d.HW) && can_vectorize(at(out), d.HW);
+      // both kernel forms take these operands; `dims` is what differs
+      auto launch = [&](auto kernel, dim3 grid, auto... dims) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, cur_stream(), at(x),
+                           at(mean, d.C), at(W, n_w), gp, bp, at(out), dims...,
+                           relu ? 1 : 0, has_affine ? 1 : 0);
+      };
+      whiten_nchw_launch(d.name, g, vec, [&](auto gconst, auto vconst) {
+        constexpr int G = decltype(gconst)::value;
+        constexpr bool V = decltype(vconst)::value;
+        launch(dwt::whiten_apply_kernel<scalar_t, G, V>,
+               nchw_elem_grid(d.HW, V ? VW : 1, d.B, n_groups), d.C, d.HW);
+      }, [&] {
+        launch(dwt::whiten_apply_gen_kernel<scalar_t>,
+               nchw_reduce_grid(d.M, 64, 1, n_groups), (int)g, d.C, d.HW, d.M);
+      });
+    }
+  });
+}
+
+void whiten_bwd_reduce(Tensor x, Tensor dout, Tensor out, Tensor mean, Tensor W,
+                       Tensor gamma, Tensor dWacc, Tensor dgb, int64_t g,
+                       bool relu, bool has_affine, int64_t parts) {
+  const NchwParts d("whiten_bwd_reduce", x, parts, {dout, out});
+  const int n_groups = d.groups(g);
+  const int64_t n_w = n_groups * g * g;
+  d.stacked({{mean, d.C}, {W, n_w}, {dWacc, n_w}, {dgb, 2 * d.C}});
+  DISPATCH_FT(x, "whiten_bwd_reduce", [&] {
+    constexpr int VW = dwt::VecTraits<scalar_t>::W;
+    const scalar_t* gp = opt_ptr<scalar_t>(gamma, has_affine);
+    for (int64_t p = 0; p < parts; ++p) {
+      const NchwBranch<scalar_t> at{d, p};
+      // g==8 vectorized variants spill (G*G + 3*G*VW live floats) — scalar
+      // loop for them (profiles/kernel_resources.md)
+      const bool vec = g <= 4 && can_vectorize(at(x), d.HW) &&
+                       can_vectorize(at(dout), d.HW) && d.M % VW == 0;
+      auto launch = [&](auto kernel, dim3 grid, auto... dims) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, cur_stream(), at(x),
+                           at(dout), at(out), at(mean, d.C), at(W, n_w), gp,
+                           at(dWacc, n_w), at(dgb, 2 * d.C), dims...,
+                           relu ? 1 : 0, has_affine ? 1 : 0);
+      };
+      whiten_nchw_launch(d.name, g, vec, [&](auto gconst, auto vconst) {
+        constexpr int G = decltype(gconst)::value;
+        constexpr bool V = decltype(vconst)::value;
+        launch(dwt::whiten_bwd_reduce_kernel<scalar_t, G, V>,
+               nchw_reduce_grid(d.M, 256, V ? VW : 1, n_groups), d.B, d.C, d.HW,
+               d.M);
+      }, [&] {
+        launch(dwt::whiten_bwd_reduce_gen_kernel<scalar_t>,
+               nchw_reduce_grid(d.M, 64, 1, n_groups), (int)g, d.C, d.HW, d.M);
+      });
+    }
+  });
+}
+
+// S / corr are empty unless train_stats
+void whiten_bwd_apply(Tensor x, Tensor dout, Tensor out, Tensor mean, Tensor W,
+                      Tensor gamma, Tensor S, Tensor corr, Tensor dx, int64_t g,
+                      bool relu, bool has_affine, bool train_stats,
+                      int64_t parts) {
+  const NchwParts d("whiten_bwd_apply", x, parts, {dout, out, dx});
+  const int n_groups = d.groups(g);
+  const int64_t n_w = n_groups * g * g;
+  const int64_t n_s = train_stats ? n_w : 0, n_corr = train_stats ? d.C : 0;
+  d.stacked({{mean, d.C}, {W, n_w}, {S, n_s}, {corr, n_corr}});
+  DISPATCH_FT(x, "whiten_bwd_apply", [&] {
+    constexpr int VW = dwt::VecTraits<scalar_t>::W;
+    const scalar_t* gp = opt_ptr<scalar_t>(gamma, has_affine);
+    for (int64_t p = 0; p < parts; ++p) {
+      const NchwBranch<scalar_t> at{d, p};
+      const bool vec = g <= 4 && can_vectorize(at(x), d.HW) &&
+                       can_vectorize(at(dx), d.HW);
+      auto launch = [&](auto kernel, dim3 grid, auto... dims) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, cur_stream(), at(x),
+                           at(dout), at(out), at(mean, d.C), at(W, n_w), gp,
+                           at(S, n_s), at(corr, n_corr), at(dx), dims...,
+                           relu ? 1 : 0, has_affine ? 1 : 0,
+                           train_stats ? 1 : 0);
+      };
+      whiten_nchw_launch(d.name, g, vec, [&](auto gconst, auto vconst) {
+        constexpr int G = decltype(gconst)::value;
+        constexpr bool V = decltype(vconst)::value;
+        launch(dwt::whiten_bwd_apply_kernel<scalar_t, G, V>,
+               nchw_elem_grid(d.HW, V ? VW : 1, d.B, n_groups), d.C, d.HW);
+      }, [&] {
+        launch(dwt::whiten_bwd_apply_gen_kernel<scalar_t>,
+               nchw_reduce_grid(d.M, 64, 1, n_groups), (int)g, d.C, d.HW, d.M);
+      });
+    }
+  });
+}
+
+void bn_stats_partial(Tensor x, Tensor acc, int64_t parts) {
+  const NchwParts d("bn_stats", x, parts);
+  d.stacked({{acc, 2 * d.C}});
+  DISPATCH_FT(x, "bn_stats", [&] {
+    constexpr int VW = dwt::VecTraits<scalar_t>::W;
+    for (int64_t p = 0; p < parts; ++p) {
+      const NchwBranch<scalar_t> at{d, p};
+      const bool vec = can_vectorize(at(x), d.HW) && d.M % VW == 0;
+      vec_launch(vec, [&](auto vconst) {
+        constexpr bool V = decltype(vconst)::value;
+        hipLaunchKernelGGL((dwt::bn_stats_partial_kernel<scalar_t, V>),
+                           nchw_reduce_grid(d.M, 256, V ? VW : 1, d.C),
+                           dim3(256), 0, cur_stream(), at(x), at(acc, 2 * d.C),
+                           d.B, d.C, d.HW, d.M);
+      });
+    }
+  });
+}
+
+void bn_apply(Tensor x, Tensor mean, Tensor istd, Tensor gamma, Tensor beta,
+              Tensor out, bool relu, bool has_affine, int64_t parts) {
+  const NchwParts d("bn_apply", x, parts, {out});
+  d.stacked({{mean, d.C}, {istd, d.C}});
+  DISPATCH_FT(x, "bn_apply", [&] {
+    constexpr int VW = dwt::VecTraits<scalar_t>::W;
+    for (int64_t p = 0; p < parts; ++p) {
+      const NchwBranch<scalar_t> at{d, p};
+      const bool vec = can_vectorize(at(x), d.HW) && can_vectorize(at(out), d.HW);
+      vec_launch(vec, [&](auto vconst) {
+        constexpr bool V = decltype(vconst)::value;
+        hipLaunchKernelGGL((dwt::bn_apply_kernel<scalar_t, V>),
+                           nchw_elem_grid(d.HW, V ? VW : 1, d.B, d.C),
+                           dim3(256), 0, cur_stream(), at(x), at(mean, d.C),
+                           at(istd, d.C), opt_ptr<scalar_t>(gamma, has_affine),
+                           opt_ptr<scalar_t>(beta, has_affine), at(out), d.C,
+                           d.HW, relu ? 1 : 0, has_affine ? 1 : 0);
+      });
+    }
+  });
+}
+
+void bn_bwd_reduce(Tensor x, Tensor dout, Tensor out, Tensor mean, Tensor istd,
+                   Tensor sums, bool relu, int64_t parts) {
+  const NchwParts d("bn_bwd_reduce", x, parts, {dout, out});
+  d.stacked({{mean, d.C}, {istd, d.C}, {sums, 2 * d.C}});
+  DISPATCH_FT(x, "bn_bwd_reduce", [&] {
+    constexpr int VW = dwt::VecTraits<scalar_t>::W;
+    for (int64_t p = 0; p < parts; ++p) {
+      const NchwBranch<scalar_t> at{d, p};
+      const bool vec = can_vectorize(at(x), d.HW) &&
+                       can_vectorize(at(dout), d.HW) && d.M % VW == 0;
+      vec_launch(vec, [&](auto vconst) {
+        constexpr bool V = decltype(vconst)::value;
+        hipLaunchKernelGGL((dwt::bn_bwd_reduce_kernel<scalar_t, V>),
+                           nchw_reduce_grid(d.M, 256, V ? VW : 1, d.C),
+                           dim3(256), 0, cur_stream(), at(x), at(dout), at(out),
+                           at(mean, d.C), at(istd, d.C), at(sums, 2 * d.C), d.B,
+                           d.C, d.HW, d.M, relu ? 1 : 0);
+      });
+    }
+  });
+}
+
+// count: the positions per branch the statistics were taken over (the GLOBAL
+// count in sync-stats mode, where sums arrives all-reduced)
+void bn_bwd_apply(Tensor x, Tensor dout, Tensor out, Tensor mean, Tensor istd,
+                  Tensor gamma, Tensor sums, Tensor dx, bool relu,
+                  bool has_affine, bool use_batch, int64_t count,
+                  int64_t parts) {
+  const NchwParts d("bn_bwd_apply", x, parts, {dout, out, dx});
+  d.stacked({{mean, d.C}, {istd, d.C}, {sums, 2 * d.C}});
+  DISPATCH_FT(x, "bn_bwd_apply", [&] {
+    constexpr int VW = dwt::VecTraits<scalar_t>::W;
+    for (int64_t p = 0; p < parts; ++p) {
+      const NchwBranch<scalar_t> at{d, p};
+      const bool vec = can_vectorize(at(x), d.HW) && can_vectorize(at(dx), d.HW);
+      vec_launch(vec, [&](auto vconst) {
+        constexpr bool V = decltype(vconst)::value;
+        hipLaunchKernelGGL((dwt::bn_bwd_apply_kernel<scalar_t, V>),
+                           nchw_elem_grid(d.HW, V ? VW : 1, d.B, d.C),
+                           dim3(256), 0, cur_stream(), at(x), at(dout), at(out),
+                           at(mean, d.C), at(istd, d.C),
+                           opt_ptr<scalar_t>(gamma, has_affine),
+                           at(sums, 2 * d.C), at(dx), d.C, d.HW,
+                           1.0f / (float)count, relu ? 1 : 0,
+                           has_affine ? 1 : 0, use_batch ? 1 : 0);
+      });
+    }
+  });
 }
 
 // ---------------------- NHWC (channels_last) launchers -------------------
@@ -2654,17 +2957,6 @@ inline void whiten_launch(bool wide, F&& f) {
   f(std::false_type{});
 }
 
-// null for an operand the kernels treat as optional (gamma / beta without an
-// affine, the join's second consumer)
-template <typename T>
-inline T* opt_ptr(const Tensor& t, bool present) {
-  return present ? t.data_ptr<T>() : nullptr;
-}
-template <typename T>
-inline T* opt_ptr(const c10::optional<Tensor>& t) {
-  return t.has_value() ? t->data_ptr<T>() : nullptr;
-}
-
 // parts = domain branches batched into one launch (grid.y); x is the full
 // (parts*B, H, W, C) NHWC storage, M = per-part positions; acc/mean/cov are
 // stacked [parts, ...].
@@ -2681,24 +2973,6 @@ void whiten_stats_partial_cl(Tensor x, Tensor acc, int64_t g, int64_t C,
       });
     });
   });
-}
-
-// count = number of positions the accumulators were summed over (the GLOBAL
-// batch count in sync-stats mode — acc is all-reduced between the partial
-// pass and this finalize)
-void whiten_stats_final(Tensor acc, Tensor mean, Tensor cov, int64_t g,
-                        int64_t n_groups, int64_t count) {
-  const int fin_threads = std::min<int64_t>(g * g, 1024);
-  hipLaunchKernelGGL(dwt::whiten_stats_final_kernel, dim3(n_groups),
-                     dim3(fin_threads), 0, cur_stream(), acc.data_ptr<float>(),
-                     mean.data_ptr<float>(), cov.data_ptr<float>(),
-                     (int)n_groups, (int)g, 1.0f / (float)count);
-}
-
-void whiten_stats_cl(Tensor x, Tensor acc, Tensor mean, Tensor cov, int64_t g,
-                     int64_t C, int64_t M, int64_t parts) {
-  whiten_stats_partial_cl(x, acc, g, C, M, parts);
-  whiten_stats_final(acc, mean, cov, g, parts * C / g, M);
 }
 
 // ---- residual join fused into the last norm site (see the kernels) ----
@@ -2848,23 +3122,6 @@ void bn_stats_partial_cl(Tensor x, Tensor acc, int64_t C, int64_t M,
   });
 }
 
-void bn_stats_final(Tensor acc, Tensor mean, Tensor istd, Tensor var_unb,
-                    int64_t C, int64_t parts, int64_t count, double eps) {
-  const float unb = count > 1 ? (float)count / (float)(count - 1) : 1.f;
-  const int total = parts * C;
-  hipLaunchKernelGGL(dwt::bn_stats_final_kernel, dim3((total + 255) / 256),
-                     dim3(256), 0, cur_stream(), acc.data_ptr<float>(),
-                     mean.data_ptr<float>(), istd.data_ptr<float>(),
-                     var_unb.data_ptr<float>(), total, (int)C,
-                     1.0f / (float)count, unb, (float)eps);
-}
-
-void bn_stats_cl(Tensor x, Tensor acc, Tensor mean, Tensor istd, Tensor var_unb,
-                 int64_t C, int64_t M, double eps, int64_t parts) {
-  bn_stats_partial_cl(x, acc, C, M, parts);
-  bn_stats_final(acc, mean, istd, var_unb, C, parts, M, eps);
-}
-
 void bn_apply_res_cl(Tensor x, Tensor mean, Tensor istd, Tensor gamma,
                      Tensor beta, c10::optional<Tensor> res, Tensor out,
                      int64_t C, int64_t M, bool relu, bool has_affine,
@@ -3012,267 +3269,6 @@ void matfn_ns_bwd(Tensor dW, Tensor W, Tensor ys, Tensor zs, Tensor svals,
                      svals.data_ptr<float>(), gdb.data_ptr<float>(),
                      S.data_ptr<float>(), corr.data_ptr<float>(), g, (float)eps,
                      (float)inv_m, (int)iters);
-}
-
-void whiten_apply(Tensor x, Tensor mean, Tensor W, Tensor gamma, Tensor beta,
-                  Tensor out, int64_t g, bool relu, bool has_affine) {
-  const int B = x.size(0), C = x.size(1);
-  const int64_t HW = x.size(2) * x.size(3);
-  const int n_groups = C / g;
-  DISPATCH_FT(x, "whiten_apply", [&] {
-    constexpr int VW = dwt::VecTraits<scalar_t>::W;
-    const bool vec = can_vectorize<scalar_t>(x, HW) && can_vectorize<scalar_t>(out, HW);
-    const int threads = 256;
-    auto launch = [&](auto gconst, auto vconst) {
-      constexpr int G = decltype(gconst)::value;
-      constexpr bool V = decltype(vconst)::value;
-      const int64_t per = V ? (HW + (int64_t)threads * VW - 1) / ((int64_t)threads * VW)
-                            : (HW + threads - 1) / threads;
-      dim3 grid(per, B, n_groups);
-      hipLaunchKernelGGL((dwt::whiten_apply_kernel<scalar_t, G, V>), grid,
-                         dim3(threads), 0, cur_stream(), x.data_ptr<scalar_t>(),
-                         mean.data_ptr<float>(), W.data_ptr<float>(),
-                         has_affine ? gamma.data_ptr<scalar_t>() : nullptr,
-                         has_affine ? beta.data_ptr<scalar_t>() : nullptr,
-                         out.data_ptr<scalar_t>(), C, HW, relu ? 1 : 0,
-                         has_affine ? 1 : 0);
-    };
-    auto pick_v = [&](auto gconst) {
-      if (vec) launch(gconst, std::true_type{});
-      else launch(gconst, std::false_type{});
-    };
-    switch (g) {
-      case 2: pick_v(std::integral_constant<int, 2>{}); break;
-      case 4: pick_v(std::integral_constant<int, 4>{}); break;
-      case 8: pick_v(std::integral_constant<int, 8>{}); break;
-      default: {
-        TORCH_CHECK(g <= 32, "whiten_apply: unsupported group size ", g);
-        const int64_t M = (int64_t)B * HW;
-        const int64_t mb = reduce_blocks(M, 64, 1, n_groups);
-        hipLaunchKernelGGL((dwt::whiten_apply_gen_kernel<scalar_t>),
-                           dim3(mb, n_groups), dim3(256), 0, cur_stream(),
-                           x.data_ptr<scalar_t>(), mean.data_ptr<float>(),
-                           W.data_ptr<float>(),
-                           has_affine ? gamma.data_ptr<scalar_t>() : nullptr,
-                           has_affine ? beta.data_ptr<scalar_t>() : nullptr,
-                           out.data_ptr<scalar_t>(), (int)g, C, HW, M,
-                           relu ? 1 : 0, has_affine ? 1 : 0);
-      }
-    }
-  });
-}
-
-void whiten_bwd_reduce(Tensor x, Tensor dout, Tensor out, Tensor mean, Tensor W,
-                       Tensor gamma, Tensor dWacc, Tensor dgb, int64_t g,
-                       bool relu, bool has_affine) {
-  const int B = x.size(0), C = x.size(1);
-  const int64_t HW = x.size(2) * x.size(3);
-  const int64_t M = (int64_t)B * HW;
-  const int n_groups = C / g;
-  DISPATCH_FT(x, "whiten_bwd_reduce", [&] {
-    constexpr int VW = dwt::VecTraits<scalar_t>::W;
-    // g==8 vectorized variants spill (G*G + 3*G*VW live floats) — scalar
-    // loop for them (profiles/kernel_resources.md)
-    const bool vec = g <= 4 && can_vectorize<scalar_t>(x, HW) &&
-                     can_vectorize<scalar_t>(dout, HW) && (M % VW == 0);
-    const int threads = 256;
-    auto launch = [&](auto gconst, auto vconst) {
-      constexpr int G = decltype(gconst)::value;
-      constexpr bool V = decltype(vconst)::value;
-      dim3 grid(reduce_blocks(M, threads, V ? VW : 1, n_groups), n_groups);
-      hipLaunchKernelGGL((dwt::whiten_bwd_reduce_kernel<scalar_t, G, V>), grid,
-                         dim3(threads), 0, cur_stream(), x.data_ptr<scalar_t>(),
-                         dout.data_ptr<scalar_t>(), out.data_ptr<scalar_t>(),
-                         mean.data_ptr<float>(), W.data_ptr<float>(),
-                         has_affine ? gamma.data_ptr<scalar_t>() : nullptr,
-                         dWacc.data_ptr<float>(), dgb.data_ptr<float>(), B, C,
-                         HW, M, relu ? 1 : 0, has_affine ? 1 : 0);
-    };
-    auto pick_v = [&](auto gconst) {
-      if (vec) launch(gconst, std::true_type{});
-      else launch(gconst, std::false_type{});
-    };
-    switch (g) {
-      case 2: pick_v(std::integral_constant<int, 2>{}); break;
-      case 4: pick_v(std::integral_constant<int, 4>{}); break;
-      case 8: pick_v(std::integral_constant<int, 8>{}); break;
-      default: {
-        TORCH_CHECK(g <= 32, "whiten_bwd_reduce: unsupported group size ", g);
-        const int64_t mb = reduce_blocks(M, 64, 1, n_groups);
-        hipLaunchKernelGGL((dwt::whiten_bwd_reduce_gen_kernel<scalar_t>),
-                           dim3(mb, n_groups), dim3(256), 0, cur_stream(),
-                           x.data_ptr<scalar_t>(), dout.data_ptr<scalar_t>(),
-                           out.data_ptr<scalar_t>(), mean.data_ptr<float>(),
-                           W.data_ptr<float>(),
-                           has_affine ? gamma.data_ptr<scalar_t>() : nullptr,
-                           dWacc.data_ptr<float>(), dgb.data_ptr<float>(),
-                           (int)g, C, HW, M, relu ? 1 : 0, has_affine ? 1 : 0);
-      }
-    }
-  });
-}
-
-void whiten_bwd_apply(Tensor x, Tensor dout, Tensor out, Tensor mean, Tensor W,
-                      Tensor gamma, Tensor S, Tensor corr, Tensor dx, int64_t g,
-                      bool relu, bool has_affine, bool train_stats) {
-  const int B = x.size(0), C = x.size(1);
-  const int64_t HW = x.size(2) * x.size(3);
-  const int n_groups = C / g;
-  DISPATCH_FT(x, "whiten_bwd_apply", [&] {
-    constexpr int VW = dwt::VecTraits<scalar_t>::W;
-    const bool vec = g <= 4 && can_vectorize<scalar_t>(x, HW) &&
-                     can_vectorize<scalar_t>(dx, HW);
-    const int threads = 256;
-    auto launch = [&](auto gconst, auto vconst) {
-      constexpr int G = decltype(gconst)::value;
-      constexpr bool V = decltype(vconst)::value;
-      const int64_t per = V ? (HW + (int64_t)threads * VW - 1) / ((int64_t)threads * VW)
-                            : (HW + threads - 1) / threads;
-      dim3 grid(per, B, n_groups);
-      hipLaunchKernelGGL((dwt::whiten_bwd_apply_kernel<scalar_t, G, V>), grid,
-                         dim3(threads), 0, cur_stream(), x.data_ptr<scalar_t>(),
-                         dout.data_ptr<scalar_t>(), out.data_ptr<scalar_t>(),
-                         mean.data_ptr<float>(), W.data_ptr<float>(),
-                         has_affine ? gamma.data_ptr<scalar_t>() : nullptr,
-                         S.data_ptr<float>(), corr.data_ptr<float>(),
-                         dx.data_ptr<scalar_t>(), C, HW, relu ? 1 : 0,
-                         has_affine ? 1 : 0, train_stats ? 1 : 0);
-    };
-    auto pick_v = [&](auto gconst) {
-      if (vec) launch(gconst, std::true_type{});
-      else launch(gconst, std::false_type{});
-    };
-    switch (g) {
-      case 2: pick_v(std::integral_constant<int, 2>{}); break;
-      case 4: pick_v(std::integral_constant<int, 4>{}); break;
-      case 8: pick_v(std::integral_constant<int, 8>{}); break;
-      default: {
-        TORCH_CHECK(g <= 32, "whiten_bwd_apply: unsupported group size ", g);
-        const int64_t M = (int64_t)B * HW;
-        const int64_t mb = reduce_blocks(M, 64, 1, n_groups);
-        hipLaunchKernelGGL((dwt::whiten_bwd_apply_gen_kernel<scalar_t>),
-                           dim3(mb, n_groups), dim3(256), 0, cur_stream(),
-                           x.data_ptr<scalar_t>(), dout.data_ptr<scalar_t>(),
-                           out.data_ptr<scalar_t>(), mean.data_ptr<float>(),
-                           W.data_ptr<float>(),
-                           has_affine ? gamma.data_ptr<scalar_t>() : nullptr,
-                           S.data_ptr<float>(), corr.data_ptr<float>(),
-                           dx.data_ptr<scalar_t>(), (int)g, C, HW, M,
-                           relu ? 1 : 0, has_affine ? 1 : 0,
-                           train_stats ? 1 : 0);
-      }
-    }
-  });
-}
-
-// ---------------------------- batchnorm ----------------------------------
-
-void bn_stats_final(Tensor acc, Tensor mean, Tensor istd, Tensor var_unb,
-                    int64_t C, int64_t parts, int64_t count, double eps);
-
-void bn_stats_partial(Tensor x, Tensor acc) {
-  const int B = x.size(0), C = x.size(1);
-  const int64_t HW = x.dim() == 4 ? x.size(2) * x.size(3) : 1;
-  const int64_t M = (int64_t)B * HW;
-  DISPATCH_FT(x, "bn_stats", [&] {
-    constexpr int VW = dwt::VecTraits<scalar_t>::W;
-    const bool vec = can_vectorize<scalar_t>(x, HW) && (M % VW == 0);
-    const int threads = 256;
-    dim3 grid(reduce_blocks(M, threads, vec ? VW : 1, C), C);
-    if (vec)
-      hipLaunchKernelGGL((dwt::bn_stats_partial_kernel<scalar_t, true>), grid,
-                         dim3(threads), 0, cur_stream(), x.data_ptr<scalar_t>(),
-                         acc.data_ptr<float>(), B, C, HW, M);
-    else
-      hipLaunchKernelGGL((dwt::bn_stats_partial_kernel<scalar_t, false>), grid,
-                         dim3(threads), 0, cur_stream(), x.data_ptr<scalar_t>(),
-                         acc.data_ptr<float>(), B, C, HW, M);
-  });
-}
-
-void bn_stats(Tensor x, Tensor acc, Tensor mean, Tensor istd, Tensor var_unb,
-              double eps) {
-  bn_stats_partial(x, acc);
-  const int64_t C = x.size(1);
-  const int64_t M = (int64_t)x.size(0) *
-                    (x.dim() == 4 ? x.size(2) * x.size(3) : 1);
-  bn_stats_final(acc, mean, istd, var_unb, C, 1, M, eps);
-}
-
-void bn_apply(Tensor x, Tensor mean, Tensor istd, Tensor gamma, Tensor beta,
-              Tensor out, bool relu, bool has_affine) {
-  const int B = x.size(0), C = x.size(1);
-  const int64_t HW = x.dim() == 4 ? x.size(2) * x.size(3) : 1;
-  DISPATCH_FT(x, "bn_apply", [&] {
-    constexpr int VW = dwt::VecTraits<scalar_t>::W;
-    const bool vec = can_vectorize<scalar_t>(x, HW) && can_vectorize<scalar_t>(out, HW);
-    const int threads = 256;
-    const int64_t per = vec ? (HW + (int64_t)threads * VW - 1) / ((int64_t)threads * VW)
-                            : (HW + threads - 1) / threads;
-    dim3 grid(per, B, C);
-    auto lp = [&](auto vconst) {
-      constexpr bool V = decltype(vconst)::value;
-      hipLaunchKernelGGL((dwt::bn_apply_kernel<scalar_t, V>), grid, dim3(threads),
-                         0, cur_stream(), x.data_ptr<scalar_t>(),
-                         mean.data_ptr<float>(), istd.data_ptr<float>(),
-                         has_affine ? gamma.data_ptr<scalar_t>() : nullptr,
-                         has_affine ? beta.data_ptr<scalar_t>() : nullptr,
-                         out.data_ptr<scalar_t>(), C, HW, relu ? 1 : 0,
-                         has_affine ? 1 : 0);
-    };
-    if (vec) lp(std::true_type{}); else lp(std::false_type{});
-  });
-}
-
-void bn_bwd_reduce(Tensor x, Tensor dout, Tensor out, Tensor mean, Tensor istd,
-                   Tensor sums, bool relu) {
-  const int B = x.size(0), C = x.size(1);
-  const int64_t HW = x.dim() == 4 ? x.size(2) * x.size(3) : 1;
-  const int64_t M = (int64_t)B * HW;
-  DISPATCH_FT(x, "bn_bwd_reduce", [&] {
-    constexpr int VW = dwt::VecTraits<scalar_t>::W;
-    const bool vec = can_vectorize<scalar_t>(x, HW) &&
-                     can_vectorize<scalar_t>(dout, HW) && (M % VW == 0);
-    const int threads = 256;
-    dim3 grid(reduce_blocks(M, threads, vec ? VW : 1, C), C);
-    auto lp = [&](auto vconst) {
-      constexpr bool V = decltype(vconst)::value;
-      hipLaunchKernelGGL((dwt::bn_bwd_reduce_kernel<scalar_t, V>), grid,
-                         dim3(threads), 0, cur_stream(), x.data_ptr<scalar_t>(),
-                         dout.data_ptr<scalar_t>(), out.data_ptr<scalar_t>(),
-                         mean.data_ptr<float>(), istd.data_ptr<float>(),
-                         sums.data_ptr<float>(), B, C, HW, M, relu ? 1 : 0);
-    };
-    if (vec) lp(std::true_type{}); else lp(std::false_type{});
-  });
-}
-
-void bn_bwd_apply(Tensor x, Tensor dout, Tensor out, Tensor mean, Tensor istd,
-                  Tensor gamma, Tensor sums, Tensor dx, bool relu,
-                  bool has_affine, bool use_batch, int64_t count) {
-  const int B = x.size(0), C = x.size(1);
-  const int64_t HW = x.dim() == 4 ? x.size(2) * x.size(3) : 1;
-  const int64_t M = (int64_t)B * HW;
-  DISPATCH_FT(x, "bn_bwd_apply", [&] {
-    constexpr int VW = dwt::VecTraits<scalar_t>::W;
-    const bool vec = can_vectorize<scalar_t>(x, HW) && can_vectorize<scalar_t>(dx, HW);
-    const int threads = 256;
-    const int64_t per = vec ? (HW + (int64_t)threads * VW - 1) / ((int64_t)threads * VW)
-                            : (HW + threads - 1) / threads;
-    dim3 grid(per, B, C);
-    auto lp = [&](auto vconst) {
-      constexpr bool V = decltype(vconst)::value;
-      hipLaunchKernelGGL((dwt::bn_bwd_apply_kernel<scalar_t, V>), grid,
-                         dim3(threads), 0, cur_stream(), x.data_ptr<scalar_t>(),
-                         dout.data_ptr<scalar_t>(), out.data_ptr<scalar_t>(),
-                         mean.data_ptr<float>(), istd.data_ptr<float>(),
-                         has_affine ? gamma.data_ptr<scalar_t>() : nullptr,
-                         sums.data_ptr<float>(), dx.data_ptr<scalar_t>(), C, HW,
-                         1.0f / (float)count, relu ? 1 : 0, has_affine ? 1 : 0,
-                         use_batch ? 1 : 0);
-    };
-    if (vec) lp(std::true_type{}); else lp(std::false_type{});
-  });
 }
 
 void maxpool_cl_fwd(Tensor x, Tensor out, Tensor idx, int64_t C, int64_t H,
@@ -3535,18 +3531,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv1x1_stats", &conv1x1_stats);
   m.def("mfma_conv2d_dgrad", &mfma_conv2d_dgrad);
   m.def("mfma_conv2d_wgrad", &mfma_conv2d_wgrad);
-  m.def("whiten_stats", &whiten_stats);
   m.def("whiten_stats_partial", &whiten_stats_partial);
   m.def("whiten_stats_partial_cl", &whiten_stats_partial_cl);
   m.def("whiten_stats_final", &whiten_stats_final);
   m.def("bn_stats_partial", &bn_stats_partial);
   m.def("bn_stats_partial_cl", &bn_stats_partial_cl);
   m.def("bn_stats_final", &bn_stats_final);
-  m.def("whiten_stats_cl", &whiten_stats_cl);
   m.def("whiten_apply_cl", &whiten_apply_cl);
   m.def("whiten_bwd_reduce_cl", &whiten_bwd_reduce_cl);
   m.def("whiten_bwd_apply_cl", &whiten_bwd_apply_cl);
-  m.def("bn_stats_cl", &bn_stats_cl);
   m.def("bn_apply_cl", &bn_apply_cl);
   m.def("bn_bwd_reduce_cl", &bn_bwd_reduce_cl);
   m.def("bn_bwd_apply_cl", &bn_bwd_apply_cl);
@@ -3563,7 +3556,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("whiten_apply", &whiten_apply);
   m.def("whiten_bwd_reduce", &whiten_bwd_reduce);
   m.def("whiten_bwd_apply", &whiten_bwd_apply);
-  m.def("bn_stats", &bn_stats);
   m.def("bn_apply", &bn_apply);
   m.def("bn_bwd_reduce", &bn_bwd_reduce);
   m.def("bn_bwd_apply", &bn_bwd_apply);

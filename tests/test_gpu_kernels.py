@@ -80,10 +80,9 @@ def test_whiten_vectorized_path(dev):
     assert torch.allclose(out_h, out_t, atol=2e-4)
 
 
-def test_whiten_bf16(dev):
-    torch.manual_seed(2)
-    c, groups = 64, 16
-    x32 = torch.randn(6, c, 16, 16, device=dev)
+def _check_whiten_bf16(dev, shape, groups):
+    c = shape[1]
+    x32 = torch.randn(*shape, device=dev)
     x = x32.to(torch.bfloat16).requires_grad_(True)
     gamma = torch.randn(c, 1, 1, device=dev, dtype=torch.bfloat16, requires_grad=True)
     beta = torch.zeros(c, 1, 1, device=dev, dtype=torch.bfloat16, requires_grad=True)
@@ -99,6 +98,81 @@ def test_whiten_bf16(dev):
     out.backward(gout)
     ref.backward(gout)
     assert torch.allclose(x.grad.float(), x2.grad.float(), atol=0.2, rtol=0.1)
+
+
+def test_whiten_bf16(dev):
+    torch.manual_seed(2)
+    _check_whiten_bf16(dev, (6, 64, 16, 16), 16)
+
+
+@pytest.mark.parametrize("shape,g", [((6, 48, 4, 4), 16), ((6, 32, 4, 4), 8)])
+def test_whiten_bf16_nchw_three_branches(dev, shape, g):
+    """The generic (g = 16) and g = 8 NCHW kernels in bf16 with HW = 16, a
+    multiple of the 8-element vector: branches 1 and 2 start at 16-byte
+    aligned offsets into x, the statistics at offsets into the stacked ones."""
+    torch.manual_seed(20)
+    _check_whiten_bf16(dev, shape, shape[1] // g)
+
+
+def test_whiten_channels_last_g8_runs_nchw(dev):
+    """g = 8 is outside the NHWC kernels' range: a channels_last input is
+    copied to NCHW and runs there, three branches."""
+    from dwt_amd.kernels.hip_ops import _whiten_layout
+    torch.manual_seed(21)
+    c, groups = 64, 8
+    x = torch.randn(6, c, 5, 7, device=dev)
+    x_cl = x.contiguous(memory_format=torch.channels_last).requires_grad_(True)
+    assert _whiten_layout(x_cl, c, 8) == "nchw"
+    x_t = x.clone().requires_grad_(True)
+    gamma = torch.randn(c, 1, 1, device=dev)
+    beta = torch.randn(c, 1, 1, device=dev)
+    ga, gb = gamma.clone().requires_grad_(True), gamma.clone().requires_grad_(True)
+    ba, bb = beta.clone().requires_grad_(True), beta.clone().requires_grad_(True)
+    cfg = _whiten_cfg(3, groups, relu=True)
+    out_h = run_whiten(x_cl, ga, ba, cfg, True)
+    out_t = run_whiten(x_t, gb, bb, cfg, False)
+    assert torch.allclose(out_h, out_t, atol=2e-4), (out_h - out_t).abs().max()
+    gout = torch.randn_like(out_t)
+    out_h.backward(gout)
+    out_t.backward(gout)
+    assert torch.allclose(x_cl.grad, x_t.grad, atol=2e-3), (x_cl.grad - x_t.grad).abs().max()
+    assert torch.allclose(ga.grad, gb.grad, atol=2e-2)
+    assert torch.allclose(ba.grad, bb.grad, atol=2e-2)
+
+
+@pytest.mark.parametrize("c,cl", [(16, False), (64, True)], ids=["nchw", "nhwc"])
+def test_whiten_eval_three_branches(dev, c, cl):
+    """Eval (running statistics, no S / corr in backward) with a distinct
+    running mean and covariance per branch, g = 4."""
+    torch.manual_seed(22)
+    parts, g = 3, 4
+    groups = c // g
+    rms = [torch.randn(1, c, 1, 1, device=dev) * 0.5 for _ in range(parts)]
+    rvs = []
+    for p in range(parts):
+        a = torch.randn(groups, g, 2 * g, device=dev)
+        rvs.append((0.5 + 0.5 * p) * torch.bmm(a, a.transpose(1, 2)) / (2 * g)
+                   + 0.1 * torch.eye(g, device=dev))
+    x = torch.randn(6, c, 5, 7, device=dev)
+    x_h = (x.contiguous(memory_format=torch.channels_last) if cl else x.clone()) \
+        .requires_grad_(True)
+    x_t = x.clone().requires_grad_(True)
+    gamma = torch.randn(c, 1, 1, device=dev)
+    beta = torch.randn(c, 1, 1, device=dev)
+    ga, gb = gamma.clone().requires_grad_(True), gamma.clone().requires_grad_(True)
+    ba, bb = beta.clone().requires_grad_(True), beta.clone().requires_grad_(True)
+    cfg = _whiten_cfg(parts, groups, training=False, relu=True)
+    out_h = run_whiten(x_h, ga, ba, cfg, True, [t.clone() for t in rms],
+                       [t.clone() for t in rvs])
+    out_t = run_whiten(x_t, gb, bb, cfg, False, rms, rvs)
+    assert out_h.is_contiguous(memory_format=torch.channels_last) == cl
+    assert torch.allclose(out_h, out_t, atol=2e-4), (out_h - out_t).abs().max()
+    gout = torch.randn_like(out_t)
+    out_h.backward(gout)
+    out_t.backward(gout)
+    assert torch.allclose(x_h.grad, x_t.grad, atol=2e-3), (x_h.grad - x_t.grad).abs().max()
+    assert torch.allclose(ga.grad, gb.grad, atol=2e-2)
+    assert torch.allclose(ba.grad, bb.grad, atol=2e-2)
 
 
 def test_whiten_ema_and_eval(dev):
@@ -160,6 +234,81 @@ def test_bn_parity(dev, spatial, relu):
     oh = _HipBatchNormMulti.apply(x, gamma, beta, rms_h[:1], rvs_h[:1], dict(cfg_e, parts=1))
     ot = BatchNormMulti.apply(x, gamma, beta, rms_t[:1], rvs_t[:1], dict(cfg_e, parts=1))
     assert torch.allclose(oh, ot, atol=1e-4)
+
+
+@pytest.mark.parametrize("c,cl", [(12, False), (128, True)], ids=["nchw", "nhwc"])
+def test_bn_eval_three_branches(dev, c, cl):
+    """Eval with a distinct running mean and variance per branch."""
+    from dwt_amd.kernels.hip_ops import _HipBatchNormMulti
+    from dwt_amd.ops.functional import BatchNormMulti
+    torch.manual_seed(23)
+    parts = 3
+    rms = [torch.randn(c, device=dev) * 0.5 for _ in range(parts)]
+    rvs = [torch.rand(c, device=dev) + 0.5 * (p + 1) for p in range(parts)]
+    x = torch.randn(6, c, 5, 7, device=dev)
+    x_h = (x.contiguous(memory_format=torch.channels_last) if cl else x.clone()) \
+        .requires_grad_(True)
+    x_t = x.clone().requires_grad_(True)
+    gamma = torch.randn(c, 1, 1, device=dev)
+    beta = torch.randn(c, 1, 1, device=dev)
+    ga, gb = gamma.clone().requires_grad_(True), gamma.clone().requires_grad_(True)
+    ba, bb = beta.clone().requires_grad_(True), beta.clone().requires_grad_(True)
+    cfg = dict(parts=parts, eps=1e-5, momentum=0.1, training=False, relu=True)
+    out_h = _HipBatchNormMulti.apply(x_h, ga, ba, [t.clone() for t in rms],
+                                     [t.clone() for t in rvs], cfg)
+    out_t = BatchNormMulti.apply(x_t, gb, bb, rms, rvs, cfg)
+    assert out_h.is_contiguous(memory_format=torch.channels_last) == cl
+    assert torch.allclose(out_h, out_t, atol=1e-4), (out_h - out_t).abs().max()
+    gout = torch.randn_like(out_t)
+    out_h.backward(gout)
+    out_t.backward(gout)
+    assert torch.allclose(x_h.grad, x_t.grad, atol=1e-3), (x_h.grad - x_t.grad).abs().max()
+    assert torch.allclose(ga.grad, gb.grad, atol=1e-2)
+    assert torch.allclose(ba.grad, bb.grad, atol=1e-2)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16],
+                         ids=["fp32", "bf16"])
+def test_bn_nchw_scalar_three_branches(dev, dtype):
+    """HW = 35 is no multiple of the vector width, so every branch takes the
+    scalar NCHW kernels (test_bn_parity's 8x8 input takes the vector form).
+    The reference is the torch Function in fp32 on the same (for bf16: the
+    bf16-rounded) values: the kernels compute in fp32 and round once, which
+    a bf16 run of the torch Function, rounding xhat and then the affine,
+    does not.  bf16 bounds are those of test_whiten_bf16."""
+    from dwt_amd.kernels.hip_ops import _HipBatchNormMulti
+    from dwt_amd.ops.functional import BatchNormMulti
+    torch.manual_seed(24)
+    c, parts = 12, 3
+    bf16 = dtype == torch.bfloat16
+    x = torch.randn(6, c, 5, 7, device=dev).to(dtype)
+    gamma = torch.randn(c, 1, 1, device=dev).to(dtype)
+    beta = torch.randn(c, 1, 1, device=dev).to(dtype)
+    rms_h = [torch.zeros(c, device=dev) for _ in range(parts)]
+    rvs_h = [torch.ones(c, device=dev) for _ in range(parts)]
+    rms_t = [t.clone() for t in rms_h]
+    rvs_t = [t.clone() for t in rvs_h]
+    cfg = dict(parts=parts, eps=1e-5, momentum=0.1, training=True, relu=True)
+
+    xa, ga, ba = (t.clone().requires_grad_(True) for t in (x, gamma, beta))
+    xb, gb, bb = (t.float().requires_grad_(True) for t in (x, gamma, beta))
+    out_h = _HipBatchNormMulti.apply(xa, ga, ba, rms_h, rvs_h, cfg)
+    out_t = BatchNormMulti.apply(xb, gb, bb, rms_t, rvs_t, cfg)
+    assert out_h.dtype == dtype
+    out_tol = dict(atol=0.1, rtol=0.05) if bf16 else dict(atol=1e-4)
+    dx_tol = dict(atol=0.2, rtol=0.1) if bf16 else dict(atol=1e-3)
+    dg_tol = dict(atol=0.2, rtol=0.1) if bf16 else dict(atol=1e-2)
+    assert torch.allclose(out_h.float(), out_t, **out_tol), \
+        (out_h.float() - out_t).abs().max()
+    for h, t in zip(rms_h + rvs_h, rms_t + rvs_t):
+        assert torch.allclose(h, t, atol=1e-4)
+    gout = torch.randn_like(out_h)
+    out_h.backward(gout)
+    out_t.backward(gout.float())
+    assert torch.allclose(xa.grad.float(), xb.grad, **dx_tol), \
+        (xa.grad.float() - xb.grad).abs().max()
+    assert torch.allclose(ga.grad.float(), gb.grad, **dg_tol)
+    assert torch.allclose(ba.grad.float(), bb.grad, **dg_tol)
 
 
 def test_losses_parity(dev):
