@@ -64,9 +64,10 @@ STATS_SHAPES = [
 def stats_mode(args):
     """Per shape: library forward, the stand-alone stats kernel on its
     output, our forward with the generic epilogue, and the fused forward +
-    stats kernel (dwt_amd.ops.mfma.conv1x1_stats).  `old/new` isolates the
-    wide-store epilogue plus the stats cost; `(lib+stats)/new` is what
-    routing a shape gains."""
+    stats kernel (dwt_amd.ops.mfma.conv1x1_stats), on the register-staged
+    main loop (`fused regs`, set_dense_glds(False)) and on the direct-to-LDS
+    one (`fused`).  `old/fused` isolates the wide-store epilogue plus the
+    stats cost; `(lib+stats)/fused` is what routing a shape gains."""
     from dwt_amd.kernels import dispatch
     from dwt_amd.ops.mfma import (conv2d_fwd, conv_stats_shape_ok,
                                   stats_acc_numel)
@@ -78,13 +79,18 @@ def stats_mode(args):
              "",
              "ms per call; `stats` = accumulator zeroing + partial + finalize "
              "kernels on the conv output; `fused` = zeroing + fused conv + "
-             "finalize kernel; `ours old` = our forward with the generic "
-             "epilogue, no statistics; `gain` = (lib fwd + stats) / fused; "
-             "`routed` is `conv_stats_shape_ok` (gain > 1.05 routes).",
+             "finalize kernel, on the direct-to-LDS main loop; `ours old` = "
+             "our forward without statistics, register-staged loop; `gain` = "
+             "(lib fwd + stats) / fused; `routed` is `conv_stats_shape_ok` "
+             "(gain > 1.05 routes).  The second table sets the fused kernel "
+             "on the register-staged loop (`fused regs`, set_dense_glds(False))"
+             " beside it.",
              "",
              "| shape | M x Cout x Cin | lib fwd | stats | ours old | fused | "
              "old/fused | gain | fused GB/s | routed |",
              "|---|---|---|---|---|---|---|---|---|---|"]
+    loops = ["", "| shape | fused regs | fused | regs/fused | fused TF |",
+             "|---|---|---|---|---|"]
     only = [t for t in args.only.split(",") if t]
     for name, cin, hw, cout, kind in STATS_SHAPES:
         if only and not any(t in name for t in only):
@@ -134,19 +140,25 @@ def stats_mode(args):
             final(acc)
 
         t_lib = timeit(lib_fn, args.iters)
+        ext.set_dense_glds(False)
         t_old = timeit(old_fn, args.iters)
+        t_regs = timeit(new_fn, args.iters)
+        ext.set_dense_glds(True)
         t_new = timeit(new_fn, args.iters)   # leaves `out` filled for stats
         t_st = timeit(stats_fn, args.iters)
         gbs = 2.0 * m * (cin + cout) / t_new / 1e9
+        tf = 2.0 * m * cin * cout / t_new / 1e12
         lines.append(
             f"| {name} ({kind}) | {m}x{cout}x{cin} | {t_lib*1e3:.3f} | "
             f"{t_st*1e3:.3f} | {t_old*1e3:.3f} | {t_new*1e3:.3f} | "
             f"{t_old/t_new:.2f}x | {(t_lib+t_st)/t_new:.2f}x | {gbs:.0f} | "
             f"{'yes' if conv_stats_shape_ok(m, cin, cout) else 'no'} |")
-        print(lines[-1], flush=True)
+        loops.append(f"| {name} ({kind}) | {t_regs*1e3:.3f} | {t_new*1e3:.3f} | "
+                     f"{t_regs/t_new:.2f}x | {tf:.0f} |")
+        print(lines[-1], loops[-1], flush=True)
         del x, out
     with open(args.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+        f.write("\n".join(lines + loops) + "\n")
     print(f"wrote {args.out}")
 
 
@@ -177,12 +189,28 @@ def main():
     assert torch.cuda.is_available()
     if args.stats:
         return stats_mode(args)
+    from dwt_amd.kernels import dispatch
     from dwt_amd.ops.mfma import conv2d_fwd, mfma_gemm
+    ext = dispatch.ext()
     dev = torch.device("cuda:0")
     lines = ["# MFMA implicit-GEMM conv/GEMM vs MIOpen/rocBLAS (bf16, NHWC)",
              "",
-             "| shape | M x N x K | GFLOP | ours ms | lib ms | ours TF | lib TF | ratio |",
-             "|---|---|---|---|---|---|---|---|"]
+             "`regs ms` = the dense kernel on the register-staged main loop "
+             "(set_dense_glds(False)), for the shapes the direct-to-LDS loop "
+             "takes; `ours` is the default.  dgrad times include the "
+             "per-call weight transpose.",
+             "",
+             "| shape | M x N x K | GFLOP | regs ms | ours ms | lib ms | "
+             "ours TF | lib TF | ratio |",
+             "|---|---|---|---|---|---|---|---|---|"]
+
+    def regs_ms(fn, dense):
+        if not dense:
+            return "-"
+        ext.set_dense_glds(False)
+        t = timeit(fn, args.iters)
+        ext.set_dense_glds(True)
+        return f"{t*1e3:.3f}"
 
     from dwt_amd.ops.mfma import conv2d_dgrad, conv2d_wgrad
 
@@ -225,10 +253,13 @@ def main():
                 continue
             if pname == "dgrad" and name == "stem7x7":
                 continue  # stem never needs dx
+            dense = k == 1 and stride == 1 and cin % 64 == 0 \
+                and cout % 64 == 0 and pname in ("fwd", "dgrad")
+            t_regs = regs_ms(ours_fn, dense)
             t_ours = timeit(ours_fn, args.iters)
             t_lib = timeit(lib_fn, args.iters)
             lines.append(f"| {name}:{pname} | {m}x{cout}x{kk} | {gflop:.1f} | "
-                         f"{t_ours*1e3:.3f} | {t_lib*1e3:.3f} | "
+                         f"{t_regs} | {t_ours*1e3:.3f} | {t_lib*1e3:.3f} | "
                          f"{gflop/t_ours/1e3:.0f} | {gflop/t_lib/1e3:.0f} | "
                          f"{t_lib/t_ours:.2f}x |")
             print(lines[-1], flush=True)
@@ -238,10 +269,11 @@ def main():
         bt = torch.randn(n, k, device=dev).to(torch.bfloat16)
         b = bt.t().contiguous()
         gflop = 2.0 * m * n * k / 1e9
+        t_regs = regs_ms(lambda: mfma_gemm(a, bt), k % 64 == 0 and n % 8 == 0)
         t_ours = timeit(lambda: mfma_gemm(a, bt), args.iters)
         t_lib = timeit(lambda: a @ b, args.iters)
         lines.append(f"| gemm:{name} | {m}x{n}x{k} | {gflop:.1f} | "
-                     f"{t_ours*1e3:.3f} | {t_lib*1e3:.3f} | "
+                     f"{t_regs} | {t_ours*1e3:.3f} | {t_lib*1e3:.3f} | "
                      f"{gflop/t_ours/1e3:.0f} | {gflop/t_lib/1e3:.0f} | "
                      f"{t_lib/t_ours:.2f}x |")
         print(lines[-1], flush=True)

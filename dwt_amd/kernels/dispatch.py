@@ -33,6 +33,9 @@ def _load():
             # DWT_AMD_NORM_WIDE=0 forces the narrow (8-byte for bf16) forms of
             # the NHWC norm kernels — the A/B switch of docs/KERNELS.md
             mod.set_norm_wide(os.environ.get("DWT_AMD_NORM_WIDE", "1") != "0")
+            # DWT_AMD_DENSE_GLDS=0 keeps the dense MFMA kernels on the
+            # register-staged main loop (set_dense_glds() in-process)
+            mod.set_dense_glds(os.environ.get("DWT_AMD_DENSE_GLDS", "1") != "0")
             _ext = mod
     except Exception as exc:  # pragma: no cover - build issues surface here
         warnings.warn(f"dwt_amd HIP extension failed to load: {exc}")

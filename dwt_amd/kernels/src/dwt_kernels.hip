@@ -3516,6 +3516,9 @@ void mfma_conv2d_wgrad(torch::Tensor dy, torch::Tensor x, torch::Tensor dw,
                        torch::Tensor ws, int64_t N, int64_t H, int64_t W,
                        int64_t Cin, int64_t P, int64_t Q, int64_t Cout,
                        int64_t KH, int64_t KW, int64_t stride, int64_t pad);
+void set_dense_glds(bool on);
+bool dense_glds_selected();
+int64_t dense_glds_launches();
 
 // defined in input_pipeline.hip
 void assemble_views(torch::Tensor images, torch::Tensor src_index,
@@ -3531,6 +3534,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv1x1_stats", &conv1x1_stats);
   m.def("mfma_conv2d_dgrad", &mfma_conv2d_dgrad);
   m.def("mfma_conv2d_wgrad", &mfma_conv2d_wgrad);
+  m.def("set_dense_glds", &set_dense_glds);
+  m.def("dense_glds_selected", &dense_glds_selected);
+  m.def("dense_glds_launches", &dense_glds_launches);
   m.def("whiten_stats_partial", &whiten_stats_partial);
   m.def("whiten_stats_partial_cl", &whiten_stats_partial_cl);
   m.def("whiten_stats_final", &whiten_stats_final);

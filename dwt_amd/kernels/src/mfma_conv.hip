@@ -284,6 +284,140 @@ DEV_INLINE void write_tile(const StageRegs& rg, unsigned short* lds) {
   }
 }
 
+// ===========================================================================
+// Direct-to-LDS main loop for the dense case: A rows of pitch K, Bt rows of
+// pitch K, K % 64 == 0.  Both tiles go global -> LDS with 16-byte LDS-DMA
+// loads (global_load_lds_dwordx4): no staging registers, no ds_write.
+//
+// LDS image.  One wave instruction writes 64 lanes x 16 B = 1 KB linearly
+// from a wave-uniform base, i.e. 8 whole rows of an UNPADDED 128-byte-row
+// tile; thread t's chunk q is tile chunk q*256 + t = row q*32 + t/8,
+// position t%8.  A +16 B row pad is impossible in this image, so the bank-
+// conflict fix is an XOR swizzle of the 16-byte chunk index: position p of
+// row r holds the row's k-chunk p ^ swz(r).  The DMA destination stays
+// linear; the permutation goes on the per-lane SOURCE address and, as the
+// same involution, on the ds_read_b128 address of the fragment reads.
+//
+// Choice of swz.  A fragment read has 16 lanes reading rows r0..r0+15 (r0 a
+// multiple of 16) at one k-chunk kc.  LDS has 64 4-byte banks = 16 groups of
+// 16 B per 256 B, so a 128-byte row covers HALF of them: the group of
+// (r, p) is (r & 1) * 8 + p.  With p = kc ^ swz(r) the 16 rows hit 16
+// distinct groups iff swz takes 8 distinct values on the even rows (and on
+// the odd rows): swz(r) = (r >> 1) & 7 does; r & 7 does not (rows r and
+// r + 8 share a parity and a value, a 2-way conflict).
+//
+// Wait structure: the plain form, two LDS buffers of A|B, the loads of
+// k-step t+1 issued before the MFMAs of k-step t and retired by vmcnt(0) +
+// __syncthreads() once per k-step.  The MFMA instruction and the ascending-k
+// order are those of the register-staged loop, so each accumulator sees the
+// same sequence of operations and the results are bit-identical.
+//
+// An LDS-DMA load cannot zero-fill: rows past the operand's end are CLAMPED
+// to its last row (never read out of bounds); the C rows / columns they
+// feed are never stored and never enter a flushed statistic.
+// ===========================================================================
+constexpr int G_TILE = BM * BK;     // halves per operand tile (16 KB)
+constexpr int G_BUF = 2 * G_TILE;   // one buffer: A tile, then B tile
+
+DEV_INLINE int glds_swz(int row) { return (row >> 1) & 7; }
+
+struct DenseSrc {
+  const bf16* a;   // tile origins: row 0, k 0
+  const bf16* b;
+  int aoff[4];     // this thread's 4 chunks: clamped row * K + swizzled k-chunk
+  int boff[4];
+};
+
+DEV_INLINE DenseSrc dense_src(const bf16* a, const bf16* b, int arows,
+                              int brows, int K) {
+  DenseSrc s;
+  s.a = a;
+  s.b = b;
+  const int t = threadIdx.x;
+  const int kc = ((t & 7) ^ glds_swz(t >> 3)) * 8;  // swz(q*32 + t/8) == swz(t/8)
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int row = q * (THREADS / 8) + (t >> 3);
+    s.aoff[q] = (row < arows ? row : arows - 1) * K + kc;
+    s.boff[q] = (row < brows ? row : brows - 1) * K + kc;
+  }
+  return s;
+}
+
+DEV_INLINE void glds16(const bf16* src, unsigned short* dst) {
+  __builtin_amdgcn_global_load_lds(
+      (const __attribute__((address_space(1))) void*)src,
+      (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+}
+
+// k-step k0 of `s` -> buf (A tile, then B tile): 8 LDS-DMA loads per wave
+DEV_INLINE void dense_issue(const DenseSrc& s, int k0, unsigned short* buf) {
+  // wave-uniform destination; the hardware adds lane * 16 B
+  unsigned short* wdst =
+      buf + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * (64 * 8);
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+    glds16(s.a + s.aoff[q] + k0, wdst + q * (THREADS * 8));
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+    glds16(s.b + s.boff[q] + k0, wdst + G_TILE + q * (THREADS * 8));
+}
+
+DEV_INLINE void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+
+// Barrier that leaves LDS-DMA loads in flight: orders this wave's own LDS
+// accesses only (__syncthreads() would also drain vmcnt).
+DEV_INLINE void lds_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
+
+// The K loop of one 128x128 tile.  On entry k-step 0 of `cur` is in
+// buf[par], landed and behind a barrier, and buf[par ^ 1] is free.  With
+// CHAIN and has_next the last k-step issues k-step 0 of `nxt` into the free
+// buffer.  Returns the buffer index of the last k-step; its fragment reads
+// are NOT yet behind a barrier, and the chained loads are still in flight.
+template <bool CHAIN>
+DEV_INLINE int dense_glds_loop(const DenseSrc& cur, const DenseSrc& nxt,
+                               bool has_next, int nk, unsigned short* lds,
+                               int par, int wm, int wn, floatx4 (&c)[4][4]) {
+  const int lane = threadIdx.x % 64;
+  const int frag_row = lane % 16;
+  // element offset of this lane's row inside a fragment, and its row swizzle
+  // (wm, wn and i * 16 are multiples of 16, so swz(row) == swz(frag_row))
+  const int rowoff = frag_row * BK;
+  const int sw = glds_swz(frag_row);
+  int b = par;
+  for (int t = 0; t < nk; ++t, b ^= 1) {
+    if (t + 1 < nk) dense_issue(cur, (t + 1) * BK, lds + (b ^ 1) * G_BUF);
+    else if (CHAIN && has_next) dense_issue(nxt, 0, lds + (b ^ 1) * G_BUF);
+    const unsigned short* la = lds + b * G_BUF + rowoff;
+    const unsigned short* lb = la + G_TILE;
+#pragma unroll
+    for (int ks = 0; ks < BK; ks += 32) {
+      const int pc = (((ks >> 3) + (lane >> 4)) ^ sw) * 8;
+      short8 afrag[4], bfrag[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        afrag[i] = *reinterpret_cast<const short8*>(la + (wm + i * 16) * BK + pc);
+        bfrag[i] = *reinterpret_cast<const short8*>(lb + (wn + i * 16) * BK + pc);
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          c[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              afrag[i], bfrag[j], c[i][j], 0, 0, 0);
+    }
+    if (t + 1 < nk) {
+      wait_vm0();        // k-step t+1 landed (this wave's share) ...
+      __syncthreads();   // ... everyone's; and buf[b] is free for k-step t+2
+    }
+  }
+  return b ^ 1;
+}
+
 // PIPE: double-buffered LDS + issue-early/write-late staging (wins for
 // long-K dense GEMMs, measured +24-34% at K>=2048); the simple
 // single-buffer loop wins for short-K and for the implicit gather path
@@ -305,7 +439,8 @@ static_assert(BM * C_PITCH <= 2 * TILE_HALFS,
 
 // lds: [buf][a|b][TILE_HALFS], 16-byte aligned; the wide epilogues overlay
 // the C tile on it from offset 0.
-template <int MODE, bool RELU, bool HAS_BIAS, bool PIPE, bool SWZ, int EPI>
+template <int MODE, bool RELU, bool HAS_BIAS, bool PIPE, bool SWZ, int EPI,
+          bool GLDS = false>
 DEV_INLINE void conv_gemm_tile(
     const bf16* __restrict__ x, const bf16* __restrict__ wgt,
     const float* __restrict__ bias, const bf16* __restrict__ res,
@@ -337,9 +472,24 @@ DEV_INLINE void conv_gemm_tile(
   const int frag_koff = (lane / 16) * 8;
   const int nk = (cp.K + BK - 1) / BK;
 
+  if (GLDS) {
+    // direct-to-LDS dense loop (the launcher guarantees K % BK == 0); lds is
+    // 2 * G_BUF halves here
+    static_assert(!GLDS || (MODE == A_DENSE && EPI != EPI_NARROW),
+                  "the direct-to-LDS loop is dense and stores 16 bytes");
+    const int arows = (int)(cp.M - m0 < BM ? cp.M - m0 : BM);
+    const int brows = cp.Cout - n0 < BN ? cp.Cout - n0 : BN;
+    const DenseSrc src = dense_src(x + m0 * cp.K, wgt + (int64_t)n0 * cp.K,
+                                   arows, brows, cp.K);
+    dense_issue(src, 0, lds);
+    wait_vm0();
+    __syncthreads();
+    dense_glds_loop<false>(src, src, false, nk, lds, 0, wm, wn, acc);
+  }
+
   StageRegs ra, rb;
   const RowCache rc = make_rows<MODE>(cp, m0);
-  if (PIPE) {
+  if (PIPE && !GLDS) {
     load_a<MODE>(x, cp, rc, 0, ra);
     load_b(wgt, cp.Cout, cp.K, n0, 0, rb);
     write_tile(ra, lds);
@@ -347,7 +497,7 @@ DEV_INLINE void conv_gemm_tile(
     __syncthreads();
   }
 
-  for (int t = 0; t < nk; ++t) {
+  for (int t = 0; !GLDS && t < nk; ++t) {
     const int cur = PIPE ? (t & 1) : 0;
     const unsigned short* la = lds + (2 * cur) * TILE_HALFS;
     const unsigned short* lb = la + TILE_HALFS;
@@ -423,7 +573,7 @@ DEV_INLINE void conv_gemm_tile(
   // ---- wide epilogue.  The simple loop left its last k-step behind a
   // barrier; the pipelined loop did not, and the staging overwrites both
   // buffers.
-  if (PIPE) __syncthreads();
+  if (PIPE || GLDS) __syncthreads();
   if (EPI == EPI_WIDE_RES) {
     // residual tile -> staging, 16 B per lane; rows / columns outside the
     // tensor stay unread (their staging slots are never stored either)
@@ -447,13 +597,14 @@ DEV_INLINE void conv_gemm_tile(
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int col = wn + j * 16 + ecol;
-    const float b = (n0 + col < cp.Cout) ? bias[n0 + col] : 0.f;
+    const float b = (HAS_BIAS && n0 + col < cp.Cout) ? bias[n0 + col] : 0.f;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         unsigned short* slot = lds + (wm + i * 16 + erow + r) * C_PITCH + col;
-        float v = acc[i][j][r] + b;
+        float v = acc[i][j][r];
+        if (HAS_BIAS) v += b;
         if (EPI == EPI_WIDE_RES) v += bf16_to_f(*slot);
         if (RELU) v = fmaxf(v, 0.f);
         *slot = f_to_bf16(v);
@@ -475,14 +626,20 @@ DEV_INLINE void conv_gemm_tile(
   }
 }
 
-template <int MODE, bool RELU, bool HAS_BIAS, bool PIPE, bool SWZ>
-__global__ __launch_bounds__(THREADS, PIPE ? 2 : 3) void conv_implicit_gemm_kernel(
+// GLDS: the direct-to-LDS dense loop with the 16-byte-store epilogue (needs
+// MODE == A_DENSE, K % BK == 0, Cout % 8 == 0 and 16-byte aligned operands;
+// PIPE is ignored).
+template <int MODE, bool RELU, bool HAS_BIAS, bool PIPE, bool SWZ,
+          bool GLDS = false>
+__global__ __launch_bounds__(THREADS, (PIPE || GLDS) ? 2 : 3)
+void conv_implicit_gemm_kernel(
     const bf16* __restrict__ x, const bf16* __restrict__ wgt,
     const float* __restrict__ bias, bf16* __restrict__ out, ConvParams cp,
     int mtiles, int ntiles) {
   __shared__ __attribute__((aligned(16)))
-  unsigned short lds[(PIPE ? 2 : 1) * 2 * TILE_HALFS];
-  conv_gemm_tile<MODE, RELU, HAS_BIAS, PIPE, SWZ, EPI_NARROW>(
+  unsigned short lds[GLDS ? 2 * G_BUF : (PIPE ? 2 : 1) * 2 * TILE_HALFS];
+  conv_gemm_tile<MODE, RELU, HAS_BIAS, PIPE, SWZ,
+                 GLDS ? EPI_WIDE : EPI_NARROW, GLDS>(
       x, wgt, bias, nullptr, out, cp, mtiles, ntiles, lds);
 }
 
@@ -552,6 +709,122 @@ DEV_INLINE void load_rows(const bf16* __restrict__ base, const int (&off)[4],
       rg.c[c] = *reinterpret_cast<const uint4*>(base + off[c] + k0);
     else
       rg.c[c] = make_uint4(0, 0, 0, 0);
+  }
+}
+
+// C staging slot of (row, col).  The padded image (pitch C_PITCH) overlays the
+// register-staged loop's padded A/B storage.  The swizzled image is exactly
+// BM * BN halves, one direct-to-LDS buffer: the fragment-layout 2-byte
+// writes of one instruction cover 4 rows 4 apart x 32 B, which at an
+// unpadded 256-B pitch would share 8 banks, so the 16-byte chunk index is
+// XORed with 2 * ((row >> 2) & 3) — four distinct 32-B bank groups; a row's
+// 16-byte reads stay one permuted 256-B row.
+template <bool SWZC>
+DEV_INLINE int c_slot(int row, int col) {
+  if (!SWZC) return row * C_PITCH + col;
+  return row * BN + ((((col >> 3) ^ (((row >> 2) & 3) << 1)) << 3) | (col & 7));
+}
+
+// Round the accumulators to bf16 IN PLACE (c then holds the stored values as
+// floats) and stage the bf16 C tile at `cst`.  Plain ds_write only: an LDS
+// atomic here would make the compiler drain every LDS-DMA load in flight.
+template <bool SWZC>
+DEV_INLINE void round_stage_tile(floatx4 (&c)[4][4], unsigned short* cst,
+                                 int wm, int wn, int erow, int ecol) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int col = wn + j * 16 + ecol;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const unsigned short u = f_to_bf16(c[i][j][r]);
+        cst[c_slot<SWZC>(wm + i * 16 + erow + r, col)] = u;
+        c[i][j][r] = bf16_to_f(u);
+      }
+    }
+  }
+}
+
+// This lane's per-column partial statistics of the ROUNDED tile -> sacc.
+template <int KIND>
+DEV_INLINE void stats_tile(const floatx4 (&c)[4][4], float* sacc, int wn,
+                           int ecol) {
+  constexpr int NV = KIND == STATS_BN ? 2 : 5;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int col = wn + j * 16 + ecol;
+    float s = 0.f, p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float v = c[i][j][r];
+        s += v;
+        if (KIND == STATS_BN) {
+          p0 += v * v;
+        } else {
+          p0 += v * quad_bcast<0x00>(v);
+          p1 += v * quad_bcast<0x55>(v);
+          p2 += v * quad_bcast<0xAA>(v);
+          p3 += v * quad_bcast<0xFF>(v);
+        }
+      }
+    }
+    if (KIND == STATS_BN) {
+      atomicAdd(&sacc[col], s);
+      atomicAdd(&sacc[BN + col], p0);
+    } else {
+      float* mine = sacc + col * NV;
+      atomicAdd(&mine[0], s);
+      atomicAdd(&mine[1], p0);
+      atomicAdd(&mine[2], p1);
+      atomicAdd(&mine[3], p2);
+      atomicAdd(&mine[4], p3);
+    }
+  }
+}
+
+// C tile out: 16 B per lane, 16 lanes per 256-B row
+template <bool SWZC>
+DEV_INLINE void store_c_tile(const unsigned short* cst, bf16* __restrict__ out,
+                             int64_t m0, int n0, int64_t M, int Cout) {
+#pragma unroll
+  for (int q = 0; q < (BM * BN / 8) / THREADS; ++q) {
+    const int idx = threadIdx.x + q * THREADS;
+    const int row = idx / (BN / 8);
+    const int cc = (idx % (BN / 8)) * 8;
+    const int64_t m = m0 + row;
+    const int n = n0 + cc;
+    if (m < M && n < Cout)
+      *reinterpret_cast<uint4*>(out + m * Cout + n) =
+          *reinterpret_cast<const uint4*>(cst + c_slot<SWZC>(row, cc));
+  }
+}
+
+// sacc -> the global accumulator of branch `part`, and zero it
+template <int KIND>
+DEV_INLINE void stats_flush(float* sacc, float* __restrict__ acc, int part,
+                            int n0, int Cout) {
+  constexpr int NV = KIND == STATS_BN ? 2 : 5;
+  for (int k = threadIdx.x; k < BN * NV; k += THREADS) {
+    const float v = sacc[k];
+    sacc[k] = 0.f;
+    if (KIND == STATS_BN) {
+      const int which = k / BN;
+      const int n = n0 + k % BN;
+      if (n < Cout)
+        atomicAdd(acc + ((int64_t)part * 2 + which) * Cout + n, v);
+    } else {
+      const int n = n0 + k / NV;
+      const int e = k % NV;
+      const int i = n & 3;
+      if (n < Cout && e <= i + 1) {
+        const int64_t grp = (int64_t)part * (Cout / 4) + n / 4;
+        const int slot = e == 0 ? i : 4 + i * 4 + (e - 1);
+        atomicAdd(acc + grp * 20 + slot, v);
+      }
+    }
   }
 }
 
@@ -680,81 +953,129 @@ __global__ __launch_bounds__(THREADS, PIPE ? 2 : 3) void conv1x1_stats_kernel(
       // ---- epilogue: round, stage C in LDS, per-column statistics ----
       // rows m >= M and columns n >= Cout hold exact zeros (their A / B
       // rows were zero-filled), so they add nothing to the sums
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int col = wn + j * 16 + ecol;
-        float s = 0.f, p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const unsigned short u = f_to_bf16(c[i][j][r]);
-            const float v = bf16_to_f(u);
-            lds[(wm + i * 16 + erow + r) * C_PITCH + col] = u;
-            s += v;
-            if (KIND == STATS_BN) {
-              p0 += v * v;
-            } else {
-              p0 += v * quad_bcast<0x00>(v);
-              p1 += v * quad_bcast<0x55>(v);
-              p2 += v * quad_bcast<0xAA>(v);
-              p3 += v * quad_bcast<0xFF>(v);
-            }
-          }
-        }
-        if (KIND == STATS_BN) {
-          atomicAdd(&sacc[col], s);
-          atomicAdd(&sacc[BN + col], p0);
-        } else {
-          float* mine = sacc + col * NV;
-          atomicAdd(&mine[0], s);
-          atomicAdd(&mine[1], p0);
-          atomicAdd(&mine[2], p1);
-          atomicAdd(&mine[3], p2);
-          atomicAdd(&mine[4], p3);
-        }
-      }
+      round_stage_tile<false>(c, lds, wm, wn, erow, ecol);
+      stats_tile<KIND>(c, sacc, wn, ecol);
       __syncthreads();
-
-      // ---- C tile out: 16 B per lane, 16 lanes per 256-B row ----
-#pragma unroll
-      for (int q = 0; q < (BM * BN / 8) / THREADS; ++q) {
-        const int idx = threadIdx.x + q * THREADS;
-        const int row = idx / (BN / 8);
-        const int cc = (idx % (BN / 8)) * 8;
-        const int64_t m = m0 + row;
-        const int n = n0 + cc;
-        if (m < cp.M && n < cp.Cout)
-          *reinterpret_cast<uint4*>(out + m * cp.Cout + n) =
-              *reinterpret_cast<const uint4*>(lds + row * C_PITCH + cc);
-      }
+      store_c_tile<false>(lds, out, m0, n0, cp.M, cp.Cout);
       __syncthreads();  // staging free again; this tile's sacc adds visible
 
       // ---- flush when the run leaves this branch or ends ----
       const int part = mt / tiles_per_part;
       if (mt + 1 == mt_end || (mt + 1) / tiles_per_part != part) {
-        for (int k = threadIdx.x; k < BN * NV; k += THREADS) {
-          const float v = sacc[k];
-          sacc[k] = 0.f;
-          if (KIND == STATS_BN) {
-            const int which = k / BN;
-            const int n = n0 + k % BN;
-            if (n < cp.Cout)
-              atomicAdd(acc + ((int64_t)part * 2 + which) * cp.Cout + n, v);
-          } else {
-            const int n = n0 + k / NV;
-            const int e = k % NV;
-            const int i = n & 3;
-            if (n < cp.Cout && e <= i + 1) {
-              const int64_t grp = (int64_t)part * (cp.Cout / 4) + n / 4;
-              const int slot = e == 0 ? i : 4 + i * 4 + (e - 1);
-              atomicAdd(acc + grp * 20 + slot, v);
-            }
-          }
-        }
+        stats_flush<KIND>(sacc, acc, part, n0, cp.Cout);
         __syncthreads();
       }
     }
+  }
+}
+
+// The same kernel on the direct-to-LDS loop (K % BK == 0), with cross-tile
+// prefetch: a workgroup's tiles form one sequence (its M-run for each of its
+// N-tiles in turn) and the last k-step of a tile issues k-step 0 of the NEXT
+// tile into the free buffer, so those loads fly under the rounding, the
+// statistics, the C staging and the start of the stores.  The buffer parity
+// carries from tile to tile.  All LDS is one array: [2][A|B] then sacc.
+//
+// Epilogue order, and why each barrier is there (buffer L = the last k-step's,
+// buffer F = the one the chained loads fill):
+//   lds_barrier        every wave finished its fragment reads of L; the
+//                      chained loads stay in flight (no vmcnt wait)
+//   round, stage C in L (swizzled, exactly one buffer, so it cannot touch
+//                      F); no statistics yet (an LDS atomic here would drain
+//                      the chained loads)
+//   vmcnt(0) + __syncthreads   C staging visible; the chained loads retired
+//                      before any global store is issued, so the wait covers
+//                      loads only, and the next tile's first fragment read of
+//                      F is behind this wait and barrier
+//   C read from L -> 16-byte global stores; statistics of the rounded
+//                      values -> sacc; [lds_barrier; flush]
+//   lds_barrier        C reads of L and the flush's sacc zeroing are done
+//                      before the next tile's k-step 1 loads land in L / its
+//                      epilogue adds to sacc; the stores stay in flight
+template <int KIND>
+__global__ __launch_bounds__(THREADS, 2) void conv1x1_stats_glds_kernel(
+    const bf16* __restrict__ x, const bf16* __restrict__ wgt,
+    bf16* __restrict__ out, float* __restrict__ acc, ConvParams cp,
+    int mtiles, int ntiles, int tiles_per_part, int nlanes, int runs) {
+  constexpr int NV = KIND == STATS_BN ? 2 : 5;   // LDS stats per column
+  __shared__ __attribute__((aligned(16)))
+  unsigned short lds[2 * G_BUF + BN * NV * 2];
+  float* sacc = reinterpret_cast<float*>(lds + 2 * G_BUF);
+  static_assert(BM * BN <= G_BUF, "C staging must fit one buffer");
+
+  // XCD-aware remap and run split: as conv1x1_stats_kernel
+  int bid = blockIdx.x;
+  {
+    const int nwg = gridDim.x;
+    const int nx = 8;
+    const int qq = nwg / nx, rr = nwg % nx;
+    const int xcd = bid % nx, idx = bid / nx;
+    bid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + idx;
+  }
+  const int nlane = bid % nlanes;
+  const int run = bid / nlanes;
+  const int mt_begin = (int)((int64_t)run * mtiles / runs);
+  const int mt_end = (int)((int64_t)(run + 1) * mtiles / runs);
+
+  const int wave = threadIdx.x / 64;
+  const int lane = threadIdx.x % 64;
+  const int wm = (wave / 2) * 64;
+  const int wn = (wave % 2) * 64;
+  const int erow = (lane / 16) * 4;
+  const int ecol = lane % 16;
+  const int nk = cp.K / BK;
+
+  for (int k = threadIdx.x; k < BN * NV; k += THREADS) sacc[k] = 0.f;
+
+  // the host guarantees M % BM == 0, so every A tile is whole
+  auto tile_src = [&](int nt, int mt) {
+    const int n0 = nt * BN;
+    return dense_src(x + (int64_t)mt * BM * cp.K, wgt + (int64_t)n0 * cp.K, BM,
+                     cp.Cout - n0 < BN ? cp.Cout - n0 : BN, cp.K);
+  };
+
+  int nt = nlane, mt = mt_begin;   // nlanes <= ntiles and runs <= mtiles
+  DenseSrc cur = tile_src(nt, mt);
+  dense_issue(cur, 0, lds);
+  wait_vm0();
+  __syncthreads();                 // also publishes the zeroed sacc
+  int par = 0;
+  for (;;) {
+    int nmt = mt + 1, nnt = nt;
+    if (nmt == mt_end) { nmt = mt_begin; nnt = nt + nlanes; }
+    const bool has_next = nnt < ntiles;
+    const DenseSrc nxt = has_next ? tile_src(nnt, nmt) : cur;
+
+    floatx4 c[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) c[i][j] = (floatx4){0.f, 0.f, 0.f, 0.f};
+    const int last =
+        dense_glds_loop<true>(cur, nxt, has_next, nk, lds, par, wm, wn, c);
+    unsigned short* cst = lds + last * G_BUF;
+
+    lds_barrier();
+    // columns n >= Cout were computed from a clamped B row: never stored,
+    // and the flush below drops their sums
+    round_stage_tile<true>(c, cst, wm, wn, erow, ecol);
+    wait_vm0();
+    __syncthreads();
+    const int n0 = nt * BN;
+    store_c_tile<true>(cst, out, (int64_t)mt * BM, n0, cp.M, cp.Cout);
+    stats_tile<KIND>(c, sacc, wn, ecol);
+    const int part = mt / tiles_per_part;
+    if (mt + 1 == mt_end || (mt + 1) / tiles_per_part != part) {
+      lds_barrier();   // every wave's sacc adds are in
+      stats_flush<KIND>(sacc, acc, part, n0, cp.Cout);
+    }
+    lds_barrier();
+
+    if (!has_next) break;
+    cur = nxt;
+    nt = nnt;
+    mt = nmt;
+    par = last ^ 1;
   }
 }
 
@@ -1126,6 +1447,56 @@ static inline int log2_if_pow2(int v) {
   return (v > 0 && (v & (v - 1)) == 0) ? __builtin_ctz((unsigned)v) : -1;
 }
 
+// The dense kernels take the direct-to-LDS loop where it applies unless this
+// is off (DWT_AMD_DENSE_GLDS=0 through dispatch, or set_dense_glds()).
+static bool g_dense_glds = true;
+static int64_t g_dense_glds_launches = 0;
+
+void set_dense_glds(bool on) { g_dense_glds = on; }
+bool dense_glds_selected() { return g_dense_glds; }
+// launches that took the direct-to-LDS loop since the extension was loaded
+int64_t dense_glds_launches() { return g_dense_glds_launches; }
+
+static inline bool aligned16(const Tensor& t) {
+  return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+}
+
+// Whether a dense GEMM A[M,K] @ Bt[N,K]^T -> out[M,N] can run on the
+// direct-to-LDS loop: whole k-steps (an LDS-DMA load cannot zero-fill), 16-byte
+// loads of both operands and 16-byte stores of the output.
+static inline bool dense_glds_ok(const Tensor& a, const Tensor& bt,
+                                 const Tensor& out, int64_t M, int64_t K,
+                                 int64_t N) {
+  return g_dense_glds && M > 0 && N > 0 && K > 0 && K % dwtmm::BK == 0 &&
+         N % 8 == 0 && aligned16(a) && aligned16(bt) && aligned16(out);
+}
+
+// The direct-to-LDS instantiations of conv_implicit_gemm_kernel (PIPE unused).
+static void launch_dense_glds(const void* a, const void* bt, const float* bias,
+                              void* out, const dwtmm::ConvParams& cp,
+                              int mtiles, int ntiles, bool relu, bool has_bias,
+                              bool swz) {
+  auto launch = [&](auto reluc, auto biasc, auto swzc) {
+    hipLaunchKernelGGL(
+        (dwtmm::conv_implicit_gemm_kernel<dwtmm::A_DENSE,
+                                          decltype(reluc)::value,
+                                          decltype(biasc)::value, false,
+                                          decltype(swzc)::value, true>),
+        dim3(mtiles * ntiles), dim3(dwtmm::THREADS), 0, dwtmm_stream(),
+        (const c10::BFloat16*)a, (const c10::BFloat16*)bt, bias,
+        (c10::BFloat16*)out, cp, mtiles, ntiles);
+  };
+  auto pick_swz = [&](auto reluc, auto biasc) {
+    if (swz) launch(reluc, biasc, std::true_type{});
+    else launch(reluc, biasc, std::false_type{});
+  };
+  if (relu) { if (has_bias) pick_swz(std::true_type{}, std::true_type{});
+              else pick_swz(std::true_type{}, std::false_type{}); }
+  else { if (has_bias) pick_swz(std::false_type{}, std::true_type{});
+         else pick_swz(std::false_type{}, std::false_type{}); }
+  ++g_dense_glds_launches;
+}
+
 // C[M,N] = A[M,K] @ Bt[N,K]^T (+bias +relu), all bf16, fp32 accumulate.
 void mfma_gemm(Tensor a, Tensor bt, Tensor bias, Tensor out, bool relu,
                bool has_bias) {
@@ -1139,6 +1510,12 @@ void mfma_gemm(Tensor a, Tensor bt, Tensor bias, Tensor out, bool relu,
   const int ntiles = (N + dwtmm::BN - 1) / dwtmm::BN;
   const bool pipe = K >= 4 * dwtmm::BK;
   const bool swz = ntiles >= 8 && mtiles * ntiles >= 16;
+  if (dense_glds_ok(a, bt, out, M, K, N)) {
+    launch_dense_glds(a.data_ptr(), bt.data_ptr(),
+                      has_bias ? bias.data_ptr<float>() : nullptr,
+                      out.data_ptr(), cp, mtiles, ntiles, relu, has_bias, swz);
+    return;
+  }
   auto run3 = [&](auto reluc, auto biasc, auto pipec, auto swzc) {
     hipLaunchKernelGGL(
         (dwtmm::conv_implicit_gemm_kernel<dwtmm::A_DENSE,
@@ -1185,6 +1562,12 @@ void mfma_conv2d_fwd(Tensor x, Tensor wgt, Tensor bias, Tensor out,
   // path's extra register pressure under PIPE regressed l3.conv2 0.91->0.60)
   const bool pipe = gemm_fast && cp.K >= 4 * dwtmm::BK;
   const bool swz = gemm_fast && ntiles >= 8 && mtiles * ntiles >= 16;
+  if (gemm_fast && dense_glds_ok(x, wgt, out, cp.M, cp.K, Cout)) {
+    launch_dense_glds(x.data_ptr(), wgt.data_ptr(),
+                      has_bias ? bias.data_ptr<float>() : nullptr,
+                      out.data_ptr(), cp, mtiles, ntiles, relu, has_bias, swz);
+    return;
+  }
   auto run = [&](auto fastc, auto reluc, auto biasc) {
     auto launch = [&](auto pipec, auto swzc) {
       hipLaunchKernelGGL(
@@ -1324,13 +1707,14 @@ void conv1x1_stats(Tensor x, Tensor wgt, Tensor out, Tensor acc, int64_t kind,
   const int mtiles = (int)(M / dwtmm::BM);
   const int ntiles = (int)((Cout + dwtmm::BN - 1) / dwtmm::BN);
   const bool pipe = cp.K >= 4 * dwtmm::BK;
+  const bool glds = dense_glds_ok(x, wgt, out, M, Cin, Cout);
   int64_t maxwg = max_workgroups;
   if (maxwg <= 0) {
     // queried once: the CU count of whichever device is current on the
     // first call serves every device (the supported boxes are homogeneous)
     static const int cus =
         at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
-    maxwg = (int64_t)cus * (pipe ? 2 : 3);
+    maxwg = (int64_t)cus * ((pipe || glds) ? 2 : 3);
   }
   const int nlanes = (int)std::min<int64_t>(maxwg, ntiles);
   const int runs = (int)std::max<int64_t>(
@@ -1346,6 +1730,21 @@ void conv1x1_stats(Tensor x, Tensor wgt, Tensor out, Tensor acc, int64_t kind,
   };
   using KBN = std::integral_constant<int, dwtmm::STATS_BN>;
   using KWH = std::integral_constant<int, dwtmm::STATS_WHITEN4>;
+  if (glds) {
+    auto launch_glds = [&](auto kindc) {
+      hipLaunchKernelGGL(
+          (dwtmm::conv1x1_stats_glds_kernel<decltype(kindc)::value>),
+          dim3(nlanes * runs), dim3(dwtmm::THREADS), 0, dwtmm_stream(),
+          (const c10::BFloat16*)x.data_ptr(),
+          (const c10::BFloat16*)wgt.data_ptr(), (c10::BFloat16*)out.data_ptr(),
+          acc.data_ptr<float>(), cp, mtiles, ntiles,
+          (int)(M / parts / dwtmm::BM), nlanes, runs);
+    };
+    if (kind == dwtmm::STATS_BN) launch_glds(KBN{});
+    else launch_glds(KWH{});
+    ++g_dense_glds_launches;
+    return;
+  }
   if (kind == dwtmm::STATS_BN) {
     if (pipe) launch(std::true_type{}, KBN{});
     else launch(std::false_type{}, KBN{});
@@ -1390,7 +1789,10 @@ void mfma_conv2d_dgrad(Tensor dy, Tensor wd, Tensor dx, int64_t N, int64_t H,
   };
   using DEN = std::integral_constant<int, dwtmm::A_DENSE>;
   using DGR = std::integral_constant<int, dwtmm::A_DGRAD>;
-  if (gemm_fast) {
+  if (gemm_fast && dense_glds_ok(dy, wd, dx, cp.M, cp.K, Cin)) {
+    launch_dense_glds(dy.data_ptr(), wd.data_ptr(), nullptr, dx.data_ptr(), cp,
+                      mtiles, ntiles, false, false, swz);
+  } else if (gemm_fast) {
     if (pipe) { if (swz) launch(DEN{}, std::true_type{}, std::true_type{});
                 else launch(DEN{}, std::true_type{}, std::false_type{}); }
     else { if (swz) launch(DEN{}, std::false_type{}, std::true_type{});

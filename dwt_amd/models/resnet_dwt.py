@@ -52,11 +52,12 @@ def _conv_with_stats(conv, x, branches, training):
     BN or g=4 whitening behind it, see ``ops.mfma.conv_stats_route``) runs on
     the MFMA kernel whose epilogue accumulates that site's raw statistics;
     ``stats_acc`` then goes to ``norm_site``.  Everything else is the plain
-    conv and ``None``."""
+    conv (for the other 1x1 stride-1 convs on the dense MFMA kernel where its
+    measured table says so, ``ops.mfma.conv1x1_dense``) and ``None``."""
     from ..ops import mfma
     route = mfma.conv_stats_route(conv, x, branches, training)
     if route is None:
-        return conv(x), None
+        return mfma.conv1x1_dense(conv, x, training), None
     kind, g, parts = route
     return mfma.conv1x1_stats(x, conv.weight, kind, g, parts)
 

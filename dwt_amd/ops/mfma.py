@@ -356,11 +356,131 @@ def conv_stats_route(conv, x: torch.Tensor, branches, training: bool):
     return kind, g, parts
 
 
+# ----------------------------------------------------------------------------
+# Routing of the 1x1 stride-1 convs to the dense MFMA kernel
+# ----------------------------------------------------------------------------
+
+# ``(pass, Cin, Cout)`` of the conv, pass in {"fwd", "dgrad"}: the shapes where
+# the dense kernel (for dgrad: including the per-call weight transpose) beat the
+# library by more than 5% in the same sitting at N = 1536
+# (profiles/conv_bench_b1536.md, direct-to-LDS loop).  The forward entries are
+# the three layer-1 shapes the stats route leaves on the plain forward; every
+# other 1x1 stride-1 forward runs as conv1x1_stats.
+_DENSE_ROUTE = {
+    ("fwd", 64, 64): 1.26, ("fwd", 256, 64): 1.15, ("fwd", 64, 256): 1.63,
+    ("dgrad", 64, 64): 1.31, ("dgrad", 256, 64): 1.61,
+    ("dgrad", 64, 256): 1.11,
+    ("dgrad", 256, 128): 1.43, ("dgrad", 512, 128): 1.36,
+    ("dgrad", 128, 512): 1.45,
+    ("dgrad", 512, 256): 1.24, ("dgrad", 1024, 256): 1.40,
+    ("dgrad", 256, 1024): 1.38,
+    ("dgrad", 1024, 512): 1.23, ("dgrad", 2048, 512): 1.35,
+    ("dgrad", 512, 2048): 1.36,
+}
+
+
+def dense_route_enabled() -> bool:
+    """``DWT_AMD_DENSE_ROUTE=0`` keeps every 1x1 dgrad and the layer-1 1x1
+    forwards on the library.  Read on every call."""
+    import os
+    return os.environ.get("DWT_AMD_DENSE_ROUTE", "1") != "0"
+
+
+def dense_route_ok(which: str, cin: int, cout: int) -> bool:
+    """Whether the measured table sends this pass of a 1x1 stride-1 conv to
+    the dense MFMA kernel."""
+    return (which, cin, cout) in _DENSE_ROUTE
+
+
+def _dense_kernel_usable(x: torch.Tensor, weight: torch.Tensor) -> bool:
+    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.bfloat16
+            and weight.dtype == torch.bfloat16 and weight.dim() == 4
+            and tuple(weight.shape[2:]) == (1, 1)
+            and x.is_contiguous(memory_format=torch.channels_last)):
+        return False
+    n, cin, h, w = x.shape
+    cout = weight.shape[0]
+    if h * w == 1 or cin % 8 or cout % 8 or weight.shape[1] != cin:
+        return False
+    from ..kernels import dispatch
+    return dispatch.available()
+
+
+def _conv1x1_backward(fn, dout, x, weight, need_dx):
+    """``(dx, dw)`` of a 1x1 stride-1 bias-free conv.  dx runs on the dense
+    kernel (dy @ W, with a per-call transposed copy of W) where the table says
+    so, dw then comes from the library alone; otherwise both are the library's,
+    exactly as before.  ``fn.dgrad_calls`` counts the routed ones."""
+    cout, cin = weight.shape[0], weight.shape[1]
+    if need_dx and dense_route_enabled() and dense_route_ok("dgrad", cin, cout) \
+            and _dense_kernel_usable(x, weight):
+        dout = dout.contiguous(memory_format=torch.channels_last)
+        dx = conv2d_dgrad(dout, weight.detach(), x.shape)
+        fn.dgrad_calls += 1
+        _, dw, _ = torch.ops.aten.convolution_backward(
+            dout, x, weight, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
+            [False, True, False])
+        return dx, dw
+    dx, dw, _ = torch.ops.aten.convolution_backward(
+        dout, x, weight, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
+        [need_dx, True, False])
+    return dx, dw
+
+
+class _Conv1x1Fn(torch.autograd.Function):
+    """A 1x1 stride-1 bias-free conv whose forward and data gradient run on
+    the dense MFMA kernel where the measured table says so, on the library
+    otherwise (always without the extension)."""
+
+    fwd_calls = 0     # forwards on the dense kernel
+    dgrad_calls = 0   # data gradients on the dense kernel
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        cout, cin = weight.shape[0], weight.shape[1]
+        if dense_route_enabled() and dense_route_ok("fwd", cin, cout) \
+                and _dense_kernel_usable(x, weight):
+            out = conv2d_fwd(x, weight.detach())
+            _Conv1x1Fn.fwd_calls += 1
+        else:
+            out = F.conv2d(x, weight)
+        ctx.save_for_backward(x, weight)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, weight = ctx.saved_tensors
+        dx, dw = _conv1x1_backward(_Conv1x1Fn, dout, x, weight,
+                                   ctx.needs_input_grad[0])
+        return dx, dw
+
+
+def conv1x1_dense(conv, x: torch.Tensor, training: bool) -> torch.Tensor:
+    """``conv(x)`` for the 1x1 stride-1 bias-free convs that do not take the
+    stats route: in training, through :class:`_Conv1x1Fn` when the dense
+    kernel can run and the table routes the forward or the data gradient of
+    this shape, else the module's own forward."""
+    if not training or not dense_route_enabled() \
+            or type(conv) is not nn.Conv2d \
+            or conv.bias is not None or conv.kernel_size != (1, 1) \
+            or conv.stride != (1, 1) or conv.padding != (0, 0) \
+            or conv.dilation != (1, 1) or conv.groups != 1:
+        return conv(x)
+    cin, cout = conv.in_channels, conv.out_channels
+    if not (dense_route_ok("fwd", cin, cout) or dense_route_ok("dgrad", cin, cout)):
+        return conv(x)
+    if not _dense_kernel_usable(x, conv.weight):
+        return conv(x)
+    return _Conv1x1Fn.apply(x, conv.weight)
+
+
 class _Conv1x1StatsFn(torch.autograd.Function):
     """Forward: the persistent MFMA GEMM with the stats epilogue.  Backward:
-    the library's dgrad / wgrad, the kernels the step runs without fusion."""
+    the data gradient on the dense MFMA kernel where the table routes it, the
+    rest on the library (see :func:`_conv1x1_backward`)."""
 
     calls = 0   # forward launches (tests assert the fused path really ran)
+    dgrad_calls = 0   # data gradients on the dense kernel
 
     @staticmethod
     def forward(ctx, x, weight, kind, g, parts, max_workgroups):
@@ -381,9 +501,8 @@ class _Conv1x1StatsFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout, _dacc):
         x, weight = ctx.saved_tensors
-        dx, dw, _ = torch.ops.aten.convolution_backward(
-            dout, x, weight, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
-            [ctx.needs_input_grad[0], True, False])
+        dx, dw = _conv1x1_backward(_Conv1x1StatsFn, dout, x, weight,
+                                   ctx.needs_input_grad[0])
         return dx, dw, None, None, None, None
 
 
