@@ -30,7 +30,11 @@
 #include <ATen/cuda/CUDAContext.h>
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <climits>
 #include <cstdint>
+#include <initializer_list>
+#include <type_traits>
 
 namespace dwtmm {
 
@@ -44,6 +48,11 @@ constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int THREADS = 256;                // 4 waves: 2x2 of 64x64
 constexpr int PAD_HALFS = 8;                // +16 B per LDS row
 constexpr int LDS_PITCH = BK + PAD_HALFS;   // halves (bf16 units)
+constexpr int TILE_HALFS = BM * LDS_PITCH;  // one padded operand tile
+constexpr int C_PITCH = BN + PAD_HALFS;     // C staging row pitch (halves)
+static_assert(BM == BN, "A and B tiles share TILE_HALFS");
+static_assert(BM * C_PITCH <= 2 * TILE_HALFS,
+              "C staging must fit the A/B storage");
 
 struct ConvParams {
   int N, H, W, Cin;      // input
@@ -284,6 +293,123 @@ DEV_INLINE void write_tile(const StageRegs& rg, unsigned short* lds) {
   }
 }
 
+// ---------------------------------------------------------------------------
+// Pieces shared by the 128x128 tile kernels (conv_gemm_tile, both stats
+// kernels, dgrad_cls_kernel).
+// ---------------------------------------------------------------------------
+
+// XCD-aware bijective block remap (guide T1): consecutive logical ids share
+// an XCD, so workgroups that read the same A rows go through one L2.
+DEV_INLINE int xcd_remap(int bid, int nwg) {
+  const int nx = 8;
+  const int qq = nwg / nx, rr = nwg % nx;
+  const int xcd = bid % nx, idx = bid / nx;
+  return (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + idx;
+}
+
+struct LaneMap {
+  int wm, wn;               // the wave's 64x64 sub-tile origin in the tile
+  int frag_row, frag_koff;  // A/B fragment: row l%16, k (l/16)*8 .. +7
+  int erow, ecol;           // C/D: lane l, reg r -> row (l/16)*4 + r, col l%16
+};
+
+DEV_INLINE LaneMap lane_map() {
+  const int wave = threadIdx.x / 64;
+  const int lane = threadIdx.x % 64;
+  LaneMap lm;
+  lm.wm = (wave / 2) * 64;
+  lm.wn = (wave % 2) * 64;
+  lm.frag_row = lane % 16;
+  lm.frag_koff = (lane / 16) * 8;
+  lm.erow = (lane / 16) * 4;
+  lm.ecol = lane % 16;
+  return lm;
+}
+
+DEV_INLINE void zero_acc(floatx4 (&acc)[4][4]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = (floatx4){0.f, 0.f, 0.f, 0.f};
+}
+
+// One BK step on the padded LDS image (row pitch LDS_PITCH): la / lb are the
+// A / B tiles' row 0.
+DEV_INLINE void mfma_kstep(const unsigned short* la, const unsigned short* lb,
+                           const LaneMap& lm, floatx4 (&acc)[4][4]) {
+#pragma unroll
+  for (int ks = 0; ks < BK; ks += 32) {
+    short8 afrag[4], bfrag[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      afrag[i] = *reinterpret_cast<const short8*>(
+          la + (lm.wm + i * 16 + lm.frag_row) * LDS_PITCH + ks + lm.frag_koff);
+      bfrag[i] = *reinterpret_cast<const short8*>(
+          lb + (lm.wn + i * 16 + lm.frag_row) * LDS_PITCH + ks + lm.frag_koff);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            afrag[i], bfrag[j], acc[i][j], 0, 0, 0);
+  }
+}
+
+// The register-staged K loop of one tile.  lds is [buf][a|b][TILE_HALFS], one
+// buffer, or two with PIPE; load_a(k0, regs) / load_b(k0, regs) issue the
+// global reads of the k-step at k0.
+//
+// PIPE: double-buffered LDS + issue-early/write-late staging (wins for
+// long-K dense GEMMs, measured +24-34% at K>=2048); the simple
+// single-buffer loop wins for short-K and for the implicit gather path
+// (within-shape A/B on the R50 shapes).
+//
+// The simple loop always leaves its last k-step behind a barrier.  The
+// pipelined loop does so only with LAST_BARRIER, for callers that go on to
+// overwrite the buffers (C staging).
+template <bool PIPE, bool LAST_BARRIER, class LoadA, class LoadB>
+DEV_INLINE void staged_k_loop(int nk, unsigned short* lds, const LaneMap& lm,
+                              floatx4 (&acc)[4][4], LoadA load_a,
+                              LoadB load_b) {
+  StageRegs ra, rb;
+  if (PIPE) {
+    load_a(0, ra);
+    load_b(0, rb);
+    write_tile(ra, lds);
+    write_tile(rb, lds + TILE_HALFS);
+    __syncthreads();
+  }
+  for (int t = 0; t < nk; ++t) {
+    const int cur = PIPE ? (t & 1) : 0;
+    unsigned short* la = lds + (2 * cur) * TILE_HALFS;
+    unsigned short* lb = la + TILE_HALFS;
+    if (PIPE) {
+      // issue next tile's global loads now — they stay in flight under the
+      // MFMA phase and are only waited for at the ds_write below
+      if (t + 1 < nk) {
+        load_a((t + 1) * BK, ra);
+        load_b((t + 1) * BK, rb);
+      }
+    } else {
+      load_a(t * BK, ra);
+      load_b(t * BK, rb);
+      write_tile(ra, la);
+      write_tile(rb, lb);
+      __syncthreads();
+    }
+    mfma_kstep(la, lb, lm, acc);
+    if (!PIPE || LAST_BARRIER || t + 1 < nk)
+      __syncthreads();  // everyone finished reading buf[cur] (and, a k-step
+                        // ago, buf[cur^1])
+    if (PIPE && t + 1 < nk) {
+      write_tile(ra, lds + (2 * (cur ^ 1)) * TILE_HALFS);
+      write_tile(rb, lds + (2 * (cur ^ 1) + 1) * TILE_HALFS);
+      __syncthreads();
+    }
+  }
+}
+
 // ===========================================================================
 // Direct-to-LDS main loop for the dense case: A rows of pitch K, Bt rows of
 // pitch K, K % 64 == 0.  Both tiles go global -> LDS with 16-byte LDS-DMA
@@ -418,11 +544,59 @@ DEV_INLINE int dense_glds_loop(const DenseSrc& cur, const DenseSrc& nxt,
   return b ^ 1;
 }
 
-// PIPE: double-buffered LDS + issue-early/write-late staging (wins for
-// long-K dense GEMMs, measured +24-34% at K>=2048); the simple
-// single-buffer loop wins for short-K and for the implicit gather path
-// (within-shape A/B on the R50 shapes).  SWZ: XCD-aware bijective block
-// remap (guide T1) — only when the grid has several N-tiles to share.
+// C staging slot of (row, col).  The padded image (pitch C_PITCH) overlays the
+// register-staged loop's padded A/B storage.  The swizzled image is exactly
+// BM * BN halves, one direct-to-LDS buffer: the fragment-layout 2-byte
+// writes of one instruction cover 4 rows 4 apart x 32 B, which at an
+// unpadded 256-B pitch would share 8 banks, so the 16-byte chunk index is
+// XORed with 2 * ((row >> 2) & 3) — four distinct 32-B bank groups; a row's
+// 16-byte reads stay one permuted 256-B row.
+template <bool SWZC>
+DEV_INLINE int c_slot(int row, int col) {
+  if (!SWZC) return row * C_PITCH + col;
+  return row * BN + ((((col >> 3) ^ (((row >> 2) & 3) << 1)) << 3) | (col & 7));
+}
+
+// Round the accumulators to bf16 IN PLACE (c then holds the stored values as
+// floats) and stage the bf16 C tile at `cst`.  Plain ds_write only: an LDS
+// atomic here would make the compiler drain every LDS-DMA load in flight.
+template <bool SWZC>
+DEV_INLINE void round_stage_tile(floatx4 (&c)[4][4], unsigned short* cst,
+                                 const LaneMap& lm) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int col = lm.wn + j * 16 + lm.ecol;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const unsigned short u = f_to_bf16(c[i][j][r]);
+        cst[c_slot<SWZC>(lm.wm + i * 16 + lm.erow + r, col)] = u;
+        c[i][j][r] = bf16_to_f(u);
+      }
+    }
+  }
+}
+
+// C tile out: 16 B per lane, 16 lanes per 256-B row
+template <bool SWZC>
+DEV_INLINE void store_c_tile(const unsigned short* cst, bf16* __restrict__ out,
+                             int64_t m0, int n0, int64_t M, int Cout) {
+#pragma unroll
+  for (int q = 0; q < (BM * BN / 8) / THREADS; ++q) {
+    const int idx = threadIdx.x + q * THREADS;
+    const int row = idx / (BN / 8);
+    const int cc = (idx % (BN / 8)) * 8;
+    const int64_t m = m0 + row;
+    const int n = n0 + cc;
+    if (m < M && n < Cout)
+      *reinterpret_cast<uint4*>(out + m * Cout + n) =
+          *reinterpret_cast<const uint4*>(cst + c_slot<SWZC>(row, cc));
+  }
+}
+
+// SWZ: the XCD block remap — only when the grid has several N-tiles to
+// share.  PIPE: see staged_k_loop.
 //
 // One tile body serves two kernels.  EPI_NARROW is the training-path
 // epilogue (optional bias / ReLU, 2-byte stores in the fragment layout).
@@ -430,12 +604,6 @@ DEV_INLINE int dense_glds_loop(const DenseSrc& cur, const DenseSrc& nxt,
 // optional residual and ReLU, fp32 adds and ONE rounding, the C tile staged
 // over the A/B LDS storage and written as 16-byte row-contiguous stores.
 enum Epilogue { EPI_NARROW = 0, EPI_WIDE = 1, EPI_WIDE_RES = 2 };
-
-constexpr int C_PITCH = BN + PAD_HALFS;  // C staging row pitch (halves)
-constexpr int TILE_HALFS = BM * LDS_PITCH;
-static_assert(BM == BN, "A and B tiles share TILE_HALFS");
-static_assert(BM * C_PITCH <= 2 * TILE_HALFS,
-              "C staging must fit the A/B storage");
 
 // lds: [buf][a|b][TILE_HALFS], 16-byte aligned; the wide epilogues overlay
 // the C tile on it from offset 0.
@@ -446,31 +614,14 @@ DEV_INLINE void conv_gemm_tile(
     const float* __restrict__ bias, const bf16* __restrict__ res,
     bf16* __restrict__ out, const ConvParams& cp, int mtiles, int ntiles,
     unsigned short* lds) {
-  int bid = blockIdx.x;
-  if (SWZ) {
-    const int nwg = mtiles * ntiles;
-    const int nx = 8;
-    const int qq = nwg / nx, rr = nwg % nx;
-    const int xcd = bid % nx, idx = bid / nx;
-    bid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + idx;
-  }
+  const int bid = SWZ ? xcd_remap(blockIdx.x, mtiles * ntiles) : blockIdx.x;
   const int64_t m0 = (int64_t)(bid / ntiles) * BM;
   const int n0 = (bid % ntiles) * BN;
-
-  const int wave = threadIdx.x / 64;
-  const int lane = threadIdx.x % 64;
-  const int wm = (wave / 2) * 64;   // wave's 64x64 sub-tile origin
-  const int wn = (wave % 2) * 64;
+  const LaneMap lm = lane_map();
+  const int nk = (cp.K + BK - 1) / BK;
 
   floatx4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = (floatx4){0.f, 0.f, 0.f, 0.f};
-
-  const int frag_row = lane % 16;
-  const int frag_koff = (lane / 16) * 8;
-  const int nk = (cp.K + BK - 1) / BK;
+  zero_acc(acc);
 
   if (GLDS) {
     // direct-to-LDS dense loop (the launcher guarantees K % BK == 0); lds is
@@ -484,81 +635,28 @@ DEV_INLINE void conv_gemm_tile(
     dense_issue(src, 0, lds);
     wait_vm0();
     __syncthreads();
-    dense_glds_loop<false>(src, src, false, nk, lds, 0, wm, wn, acc);
+    dense_glds_loop<false>(src, src, false, nk, lds, 0, lm.wm, lm.wn, acc);
+    __syncthreads();  // the staging below overwrites the last k-step's buffer
+  } else {
+    const RowCache rc = make_rows<MODE>(cp, m0);
+    staged_k_loop<PIPE, EPI != EPI_NARROW>(
+        nk, lds, lm, acc,
+        [&](int k0, StageRegs& rg) { load_a<MODE>(x, cp, rc, k0, rg); },
+        [&](int k0, StageRegs& rg) {
+          load_b(wgt, cp.Cout, cp.K, n0, k0, rg);
+        });
   }
 
-  StageRegs ra, rb;
-  const RowCache rc = make_rows<MODE>(cp, m0);
-  if (PIPE && !GLDS) {
-    load_a<MODE>(x, cp, rc, 0, ra);
-    load_b(wgt, cp.Cout, cp.K, n0, 0, rb);
-    write_tile(ra, lds);
-    write_tile(rb, lds + TILE_HALFS);
-    __syncthreads();
-  }
-
-  for (int t = 0; !GLDS && t < nk; ++t) {
-    const int cur = PIPE ? (t & 1) : 0;
-    const unsigned short* la = lds + (2 * cur) * TILE_HALFS;
-    const unsigned short* lb = la + TILE_HALFS;
-    if (PIPE) {
-      // issue next tile's global loads now — they stay in flight under the
-      // MFMA phase and are only waited for at the ds_write below
-      if (t + 1 < nk) {
-        load_a<MODE>(x, cp, rc, (t + 1) * BK, ra);
-        load_b(wgt, cp.Cout, cp.K, n0, (t + 1) * BK, rb);
-      }
-    } else {
-      load_a<MODE>(x, cp, rc, t * BK, ra);
-      load_b(wgt, cp.Cout, cp.K, n0, t * BK, rb);
-      write_tile(ra, lds);
-      write_tile(rb, lds + TILE_HALFS);
-      __syncthreads();
-    }
-#pragma unroll
-    for (int ks = 0; ks < BK; ks += 32) {
-      short8 afrag[4], bfrag[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const unsigned short* pa =
-            la + (wm + i * 16 + frag_row) * LDS_PITCH + ks + frag_koff;
-        afrag[i] = *reinterpret_cast<const short8*>(pa);
-        const unsigned short* pb =
-            lb + (wn + i * 16 + frag_row) * LDS_PITCH + ks + frag_koff;
-        bfrag[i] = *reinterpret_cast<const short8*>(pb);
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              afrag[i], bfrag[j], acc[i][j], 0, 0, 0);
-    }
-    if (PIPE) {
-      if (t + 1 < nk) {
-        __syncthreads();  // everyone finished reading buf[cur^1] (tile t-1)
-        write_tile(ra, lds + (2 * (cur ^ 1)) * TILE_HALFS);
-        write_tile(rb, lds + (2 * (cur ^ 1) + 1) * TILE_HALFS);
-        __syncthreads();
-      }
-    } else {
-      __syncthreads();
-    }
-  }
-
-  // epilogue: lane l, reg r -> row (l/16)*4 + r, col l%16 of each 16x16 frag
-  const int erow = (lane / 16) * 4;
-  const int ecol = lane % 16;
   if (EPI == EPI_NARROW) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int64_t m = m0 + wm + i * 16 + erow + r;
+        const int64_t m = m0 + lm.wm + i * 16 + lm.erow + r;
         if (m >= cp.M) continue;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const int n = n0 + wn + j * 16 + ecol;
+          const int n = n0 + lm.wn + j * 16 + lm.ecol;
           if (n >= cp.Cout) continue;
           float v = acc[i][j][r];
           if (HAS_BIAS) v += bias[n];
@@ -570,10 +668,7 @@ DEV_INLINE void conv_gemm_tile(
     return;
   }
 
-  // ---- wide epilogue.  The simple loop left its last k-step behind a
-  // barrier; the pipelined loop did not, and the staging overwrites both
-  // buffers.
-  if (PIPE || GLDS) __syncthreads();
+  // ---- wide epilogue: the last k-step is behind a barrier ----
   if (EPI == EPI_WIDE_RES) {
     // residual tile -> staging, 16 B per lane; rows / columns outside the
     // tensor stay unread (their staging slots are never stored either)
@@ -596,13 +691,14 @@ DEV_INLINE void conv_gemm_tile(
   // and writes the bf16 result back to the same slot
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const int col = wn + j * 16 + ecol;
+    const int col = lm.wn + j * 16 + lm.ecol;
     const float b = (HAS_BIAS && n0 + col < cp.Cout) ? bias[n0 + col] : 0.f;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        unsigned short* slot = lds + (wm + i * 16 + erow + r) * C_PITCH + col;
+        unsigned short* slot =
+            lds + c_slot<false>(lm.wm + i * 16 + lm.erow + r, col);
         float v = acc[i][j][r];
         if (HAS_BIAS) v += b;
         if (EPI == EPI_WIDE_RES) v += bf16_to_f(*slot);
@@ -612,18 +708,7 @@ DEV_INLINE void conv_gemm_tile(
     }
   }
   __syncthreads();
-  // ---- C tile out: 16 B per lane, 16 lanes per 256-B row ----
-#pragma unroll
-  for (int q = 0; q < (BM * BN / 8) / THREADS; ++q) {
-    const int idx = threadIdx.x + q * THREADS;
-    const int row = idx / (BN / 8);
-    const int cc = (idx % (BN / 8)) * 8;
-    const int64_t m = m0 + row;
-    const int n = n0 + cc;
-    if (m < cp.M && n < cp.Cout)
-      *reinterpret_cast<uint4*>(out + m * cp.Cout + n) =
-          *reinterpret_cast<const uint4*>(lds + row * C_PITCH + cc);
-  }
+  store_c_tile<false>(lds, out, m0, n0, cp.M, cp.Cout);
 }
 
 // GLDS: the direct-to-LDS dense loop with the 16-byte-store epilogue (needs
@@ -712,40 +797,6 @@ DEV_INLINE void load_rows(const bf16* __restrict__ base, const int (&off)[4],
   }
 }
 
-// C staging slot of (row, col).  The padded image (pitch C_PITCH) overlays the
-// register-staged loop's padded A/B storage.  The swizzled image is exactly
-// BM * BN halves, one direct-to-LDS buffer: the fragment-layout 2-byte
-// writes of one instruction cover 4 rows 4 apart x 32 B, which at an
-// unpadded 256-B pitch would share 8 banks, so the 16-byte chunk index is
-// XORed with 2 * ((row >> 2) & 3) — four distinct 32-B bank groups; a row's
-// 16-byte reads stay one permuted 256-B row.
-template <bool SWZC>
-DEV_INLINE int c_slot(int row, int col) {
-  if (!SWZC) return row * C_PITCH + col;
-  return row * BN + ((((col >> 3) ^ (((row >> 2) & 3) << 1)) << 3) | (col & 7));
-}
-
-// Round the accumulators to bf16 IN PLACE (c then holds the stored values as
-// floats) and stage the bf16 C tile at `cst`.  Plain ds_write only: an LDS
-// atomic here would make the compiler drain every LDS-DMA load in flight.
-template <bool SWZC>
-DEV_INLINE void round_stage_tile(floatx4 (&c)[4][4], unsigned short* cst,
-                                 int wm, int wn, int erow, int ecol) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int col = wn + j * 16 + ecol;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const unsigned short u = f_to_bf16(c[i][j][r]);
-        cst[c_slot<SWZC>(wm + i * 16 + erow + r, col)] = u;
-        c[i][j][r] = bf16_to_f(u);
-      }
-    }
-  }
-}
-
 // This lane's per-column partial statistics of the ROUNDED tile -> sacc.
 template <int KIND>
 DEV_INLINE void stats_tile(const floatx4 (&c)[4][4], float* sacc, int wn,
@@ -785,23 +836,6 @@ DEV_INLINE void stats_tile(const floatx4 (&c)[4][4], float* sacc, int wn,
   }
 }
 
-// C tile out: 16 B per lane, 16 lanes per 256-B row
-template <bool SWZC>
-DEV_INLINE void store_c_tile(const unsigned short* cst, bf16* __restrict__ out,
-                             int64_t m0, int n0, int64_t M, int Cout) {
-#pragma unroll
-  for (int q = 0; q < (BM * BN / 8) / THREADS; ++q) {
-    const int idx = threadIdx.x + q * THREADS;
-    const int row = idx / (BN / 8);
-    const int cc = (idx % (BN / 8)) * 8;
-    const int64_t m = m0 + row;
-    const int n = n0 + cc;
-    if (m < M && n < Cout)
-      *reinterpret_cast<uint4*>(out + m * Cout + n) =
-          *reinterpret_cast<const uint4*>(cst + c_slot<SWZC>(row, cc));
-  }
-}
-
 // sacc -> the global accumulator of branch `part`, and zero it
 template <int KIND>
 DEV_INLINE void stats_flush(float* sacc, float* __restrict__ acc, int part,
@@ -833,38 +867,21 @@ __global__ __launch_bounds__(THREADS, PIPE ? 2 : 3) void conv1x1_stats_kernel(
     const bf16* __restrict__ x, const bf16* __restrict__ wgt,
     bf16* __restrict__ out, float* __restrict__ acc, ConvParams cp,
     int mtiles, int ntiles, int tiles_per_part, int nlanes, int runs) {
-  constexpr int TILE = BM * LDS_PITCH;
-  constexpr int NBUF = PIPE ? 2 : 1;
   constexpr int NV = KIND == STATS_BN ? 2 : 5;   // LDS stats per column
-  // [buf][a|b][TILE]; the C staging tile overlays it from offset 0
-  __shared__ __attribute__((aligned(16))) unsigned short lds[NBUF * 2 * TILE];
+  // [buf][a|b][TILE_HALFS]; the C staging tile overlays it from offset 0
+  __shared__ __attribute__((aligned(16)))
+  unsigned short lds[(PIPE ? 2 : 1) * 2 * TILE_HALFS];
   __shared__ float sacc[BN * NV];
-  static_assert(BM * C_PITCH <= 2 * TILE, "C staging must fit the A/B storage");
 
-  // XCD-aware bijective remap (as SWZ above): consecutive logical ids share
-  // an XCD, so the workgroups walking the same M-run for neighbouring
+  // XCD remap: the workgroups walking the same M-run for neighbouring
   // N-tiles read their A tiles through one L2
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x;
-    const int nx = 8;
-    const int qq = nwg / nx, rr = nwg % nx;
-    const int xcd = bid % nx, idx = bid / nx;
-    bid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + idx;
-  }
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);
   const int nlane = bid % nlanes;
   const int run = bid / nlanes;
   const int mt_begin = (int)((int64_t)run * mtiles / runs);
   const int mt_end = (int)((int64_t)(run + 1) * mtiles / runs);
 
-  const int wave = threadIdx.x / 64;
-  const int lane = threadIdx.x % 64;
-  const int wm = (wave / 2) * 64;
-  const int wn = (wave % 2) * 64;
-  const int frag_row = lane % 16;
-  const int frag_koff = (lane / 16) * 8;
-  const int erow = (lane / 16) * 4;
-  const int ecol = lane % 16;
+  const LaneMap lm = lane_map();
   const int nk = (cp.K + BK - 1) / BK;
 
   // A and B tiles stage with one chunk map: element offsets row*K + kc from
@@ -887,74 +904,21 @@ __global__ __launch_bounds__(THREADS, PIPE ? 2 : 3) void conv1x1_stats_kernel(
       const int64_t m0 = (int64_t)mt * BM;
 
       floatx4 c[4][4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) c[i][j] = (floatx4){0.f, 0.f, 0.f, 0.f};
-
-      StageRegs ra, rb;
+      zero_acc(c);
       const bf16* xa = x + m0 * cp.K;
       const int arows = (int)(cp.M - m0 < BM ? cp.M - m0 : BM);
-      if (PIPE) {
-        load_rows(xa, off, arows, cp.K, 0, ra);
-        load_rows(wb, off, brows, cp.K, 0, rb);
-        write_tile(ra, lds);
-        write_tile(rb, lds + TILE);
-        __syncthreads();
-      }
-      for (int t = 0; t < nk; ++t) {
-        const int cur = PIPE ? (t & 1) : 0;
-        unsigned short* la = lds + (2 * cur) * TILE;
-        unsigned short* lb = la + TILE;
-        if (PIPE) {
-          if (t + 1 < nk) {
-            load_rows(xa, off, arows, cp.K, (t + 1) * BK, ra);
-            load_rows(wb, off, brows, cp.K, (t + 1) * BK, rb);
-          }
-        } else {
-          load_rows(xa, off, arows, cp.K, t * BK, ra);
-          load_rows(wb, off, brows, cp.K, t * BK, rb);
-          write_tile(ra, la);
-          write_tile(rb, lb);
-          __syncthreads();
-        }
-#pragma unroll
-        for (int ks = 0; ks < BK; ks += 32) {
-          short8 afrag[4], bfrag[4];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            afrag[i] = *reinterpret_cast<const short8*>(
-                la + (wm + i * 16 + frag_row) * LDS_PITCH + ks + frag_koff);
-            bfrag[i] = *reinterpret_cast<const short8*>(
-                lb + (wn + i * 16 + frag_row) * LDS_PITCH + ks + frag_koff);
-          }
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-              c[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                  afrag[i], bfrag[j], c[i][j], 0, 0, 0);
-        }
-        if (PIPE) {
-          // the last k-step also ends on a barrier here: the C staging
-          // below overwrites both buffers
-          __syncthreads();
-          if (t + 1 < nk) {
-            const int nxt = cur ^ 1;
-            write_tile(ra, lds + (2 * nxt) * TILE);
-            write_tile(rb, lds + (2 * nxt + 1) * TILE);
-            __syncthreads();
-          }
-        } else {
-          __syncthreads();
-        }
-      }
+      // the last k-step ends on a barrier: the C staging below overwrites
+      // both buffers
+      staged_k_loop<PIPE, true>(
+          nk, lds, lm, c,
+          [&](int k0, StageRegs& rg) { load_rows(xa, off, arows, cp.K, k0, rg); },
+          [&](int k0, StageRegs& rg) { load_rows(wb, off, brows, cp.K, k0, rg); });
 
       // ---- epilogue: round, stage C in LDS, per-column statistics ----
       // rows m >= M and columns n >= Cout hold exact zeros (their A / B
       // rows were zero-filled), so they add nothing to the sums
-      round_stage_tile<false>(c, lds, wm, wn, erow, ecol);
-      stats_tile<KIND>(c, sacc, wn, ecol);
+      round_stage_tile<false>(c, lds, lm);
+      stats_tile<KIND>(c, sacc, lm.wn, lm.ecol);
       __syncthreads();
       store_c_tile<false>(lds, out, m0, n0, cp.M, cp.Cout);
       __syncthreads();  // staging free again; this tile's sacc adds visible
@@ -1003,26 +967,14 @@ __global__ __launch_bounds__(THREADS, 2) void conv1x1_stats_glds_kernel(
   float* sacc = reinterpret_cast<float*>(lds + 2 * G_BUF);
   static_assert(BM * BN <= G_BUF, "C staging must fit one buffer");
 
-  // XCD-aware remap and run split: as conv1x1_stats_kernel
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x;
-    const int nx = 8;
-    const int qq = nwg / nx, rr = nwg % nx;
-    const int xcd = bid % nx, idx = bid / nx;
-    bid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + idx;
-  }
+  // XCD remap and run split: as conv1x1_stats_kernel
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);
   const int nlane = bid % nlanes;
   const int run = bid / nlanes;
   const int mt_begin = (int)((int64_t)run * mtiles / runs);
   const int mt_end = (int)((int64_t)(run + 1) * mtiles / runs);
 
-  const int wave = threadIdx.x / 64;
-  const int lane = threadIdx.x % 64;
-  const int wm = (wave / 2) * 64;
-  const int wn = (wave % 2) * 64;
-  const int erow = (lane / 16) * 4;
-  const int ecol = lane % 16;
+  const LaneMap lm = lane_map();
   const int nk = cp.K / BK;
 
   for (int k = threadIdx.x; k < BN * NV; k += THREADS) sacc[k] = 0.f;
@@ -1047,23 +999,20 @@ __global__ __launch_bounds__(THREADS, 2) void conv1x1_stats_glds_kernel(
     const DenseSrc nxt = has_next ? tile_src(nnt, nmt) : cur;
 
     floatx4 c[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) c[i][j] = (floatx4){0.f, 0.f, 0.f, 0.f};
-    const int last =
-        dense_glds_loop<true>(cur, nxt, has_next, nk, lds, par, wm, wn, c);
+    zero_acc(c);
+    const int last = dense_glds_loop<true>(cur, nxt, has_next, nk, lds, par,
+                                           lm.wm, lm.wn, c);
     unsigned short* cst = lds + last * G_BUF;
 
     lds_barrier();
     // columns n >= Cout were computed from a clamped B row: never stored,
     // and the flush below drops their sums
-    round_stage_tile<true>(c, cst, wm, wn, erow, ecol);
+    round_stage_tile<true>(c, cst, lm);
     wait_vm0();
     __syncthreads();
     const int n0 = nt * BN;
     store_c_tile<true>(cst, out, (int64_t)mt * BM, n0, cp.M, cp.Cout);
-    stats_tile<KIND>(c, sacc, wn, ecol);
+    stats_tile<KIND>(c, sacc, lm.wn, lm.ecol);
     const int part = mt / tiles_per_part;
     if (mt + 1 == mt_end || (mt + 1) / tiles_per_part != part) {
       lds_barrier();   // every wave's sacc adds are in
@@ -1306,16 +1255,10 @@ __global__ __launch_bounds__(THREADS, 3) void dgrad_cls_kernel(
   const int bid = blockIdx.x;
   const int64_t m0 = (int64_t)(bid / ntiles) * BM;
   const int n0 = (bid % ntiles) * BN;
-  const int wave = threadIdx.x / 64;
-  const int lane = threadIdx.x % 64;
-  const int wm = (wave / 2) * 64;
-  const int wn = (wave % 2) * 64;
+  const LaneMap lm = lane_map();
 
   floatx4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = (floatx4){0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
 
   // row cache: class position m -> (n, hh, ww)
   int rcP[4], rcQ[4];
@@ -1340,8 +1283,6 @@ __global__ __launch_bounds__(THREADS, 3) void dgrad_cls_kernel(
     }
   }
 
-  const int frag_row = lane % 16;
-  const int frag_koff = (lane / 16) * 8;
   const int nk = (gp.K + BK - 1) / BK;
   const int t = threadIdx.x;
 
@@ -1384,34 +1325,16 @@ __global__ __launch_bounds__(THREADS, 3) void dgrad_cls_kernel(
       *reinterpret_cast<uint4*>(lds_b + row * LDS_PITCH + kc) = val;
     }
     __syncthreads();
-#pragma unroll
-    for (int ks = 0; ks < BK; ks += 32) {
-      short8 afrag[4], bfrag[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        afrag[i] = *reinterpret_cast<const short8*>(
-            lds_a + (wm + i * 16 + frag_row) * LDS_PITCH + ks + frag_koff);
-        bfrag[i] = *reinterpret_cast<const short8*>(
-            lds_b + (wn + i * 16 + frag_row) * LDS_PITCH + ks + frag_koff);
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              afrag[i], bfrag[j], acc[i][j], 0, 0, 0);
-    }
+    mfma_kstep(lds_a, lds_b, lm, acc);
     __syncthreads();
   }
 
   // epilogue: scatter to dx[n, hh*s+ch, ww*s+cw, ci]
-  const int erow = (lane / 16) * 4;
-  const int ecol = lane % 16;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int64_t m = m0 + wm + i * 16 + erow + r;
+      const int64_t m = m0 + lm.wm + i * 16 + lm.erow + r;
       if (m >= gp.M) continue;
       const int ww = (int)(m % gp.Wc);
       const int64_t nh = m / gp.Wc;
@@ -1422,7 +1345,7 @@ __global__ __launch_bounds__(THREADS, 3) void dgrad_cls_kernel(
       const int64_t obase = (((int64_t)n * gp.H + h) * gp.W + w) * gp.Cin;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const int col = n0 + wn + j * 16 + ecol;
+        const int col = n0 + lm.wn + j * 16 + lm.ecol;
         if (col >= gp.Cin) continue;
         *reinterpret_cast<unsigned short*>(dx + obase + col) =
             f_to_bf16(acc[i][j][r]);
@@ -1443,10 +1366,128 @@ static inline hipStream_t dwtmm_stream() {
   return at::cuda::getCurrentCUDAStream().stream();
 }
 
-static inline int log2_if_pow2(int v) {
-  return (v > 0 && (v & (v - 1)) == 0) ? __builtin_ctz((unsigned)v) : -1;
+static inline int log2_if_pow2(int64_t v) {
+  return (v > 0 && (v & (v - 1)) == 0) ? __builtin_ctzll((uint64_t)v) : -1;
 }
 
+// ---- runtime values -> template arguments --------------------------------
+// static_dispatch(f, a, b, ...) calls the generic lambda f with one
+// std::integral_constant per argument: a bool arrives as std::true_type /
+// std::false_type, a OneOf<V0, V1, ...>{v} as the integral_constant<int, Vi>
+// with Vi == v.  f is instantiated for every combination, so pass only what
+// can vary at the call site.
+template <int... Vs>
+struct OneOf { int64_t v; };
+
+template <class F>
+static void static_dispatch(F&& f) { f(); }
+
+template <class F, int V0, int... Vs, class... Rest>
+static void static_dispatch(F&& f, OneOf<V0, Vs...> e, Rest... rest);
+
+template <class F, class... Rest>
+static void static_dispatch(F&& f, bool b, Rest... rest) {
+  auto bind = [&](auto c) {
+    static_dispatch([&](auto... cs) { f(c, cs...); }, rest...);
+  };
+  if (b) bind(std::true_type{});
+  else bind(std::false_type{});
+}
+
+template <class F, int V0, int... Vs, class... Rest>
+static void static_dispatch(F&& f, OneOf<V0, Vs...> e, Rest... rest) {
+  if (e.v == V0) {
+    static_dispatch(
+        [&](auto... cs) { f(std::integral_constant<int, V0>{}, cs...); },
+        rest...);
+    return;
+  }
+  if constexpr (sizeof...(Vs) > 0)
+    static_dispatch(f, OneOf<Vs...>{e.v}, rest...);
+  else
+    TORCH_CHECK(false, "static_dispatch: no instantiation for value ", e.v);
+}
+
+// ---- argument checks, ConvParams and the tile plan ------------------------
+
+struct Operand {
+  const char* name;
+  const Tensor& t;
+  at::ScalarType dtype;
+  int64_t numel;   // what the passed geometry says
+};
+
+static void check_operands(const char* who,
+                           std::initializer_list<Operand> ops) {
+  for (const Operand& o : ops)
+    TORCH_CHECK(o.t.defined() && o.t.is_cuda() &&
+                    o.t.scalar_type() == o.dtype && o.t.numel() == o.numel,
+                who, ": ", o.name, " must be a ", o.dtype, " GPU tensor of ",
+                o.numel, " elements");
+}
+
+// C[M,N] = A[M,K] @ Bt[N,K]^T
+static dwtmm::ConvParams gemm_params(const char* who, int64_t M, int64_t K,
+                                     int64_t N) {
+  TORCH_CHECK(M > 0 && N > 0 && K >= 0 && K <= INT_MAX && N <= INT_MAX, who,
+              ": GEMM extents ", M, " x ", K, " x ", N);
+  dwtmm::ConvParams cp{};
+  cp.M = M; cp.K = (int)K; cp.Cout = (int)N;
+  return cp;
+}
+
+// Conv geometry as the entry points receive it.  For dgrad, Cout is Cdy.
+struct ConvGeom {
+  int64_t N, H, W, Cin, P, Q, Cout, KH, KW, stride, pad;
+  // a plain GEMM over the positions
+  bool unit() const { return KH == 1 && KW == 1 && stride == 1 && pad == 0; }
+};
+
+// fwd: M = N*P*Q rows of K = KH*KW*Cin, Cout columns.  dgrad: M = N*H*W rows
+// of K = KH*KW*Cdy, Cin columns.
+static dwtmm::ConvParams conv_params(const char* who, const ConvGeom& g,
+                                     bool dgrad) {
+  TORCH_CHECK(g.N > 0 && g.H > 0 && g.W > 0 && g.Cin > 0 && g.P > 0 &&
+                  g.Q > 0 && g.Cout > 0 && g.KH > 0 && g.KW > 0 &&
+                  g.stride > 0 && g.pad >= 0,
+              who, ": conv geometry");
+  const int64_t cfast = dgrad ? g.Cout : g.Cin;   // the K-fastest channels
+  dwtmm::ConvParams cp =
+      gemm_params(who, dgrad ? g.N * g.H * g.W : g.N * g.P * g.Q,
+                  g.KH * g.KW * cfast, dgrad ? g.Cin : g.Cout);
+  cp.N = g.N; cp.H = g.H; cp.W = g.W; cp.Cin = g.Cin;
+  cp.P = g.P; cp.Q = g.Q;
+  cp.KH = g.KH; cp.KW = g.KW; cp.stride = g.stride; cp.pad = g.pad;
+  cp.Cdy = dgrad ? g.Cout : 0;
+  cp.cShift = log2_if_pow2(cfast);
+  return cp;
+}
+
+struct TilePlan {
+  int mtiles, ntiles;
+  bool gemm_fast;   // the A operand is a dense [M, K] matrix (A_DENSE)
+  bool pipe, swz;   // PIPE / SWZ of the tile kernels
+};
+
+// unit: 1x1 stride-1 pad-0 geometry; cfast: the K-fastest channel count.
+static TilePlan tile_plan(const char* who, const dwtmm::ConvParams& cp,
+                          bool unit, int64_t cfast) {
+  const int64_t mt = (cp.M + dwtmm::BM - 1) / dwtmm::BM;
+  const int64_t nt = (cp.Cout + dwtmm::BN - 1) / dwtmm::BN;
+  TORCH_CHECK(mt * nt < (int64_t)1 << 31, who, ": grid of ", mt, " x ", nt,
+              " tiles does not fit 32 bits");
+  TilePlan tp;
+  tp.mtiles = (int)mt;
+  tp.ntiles = (int)nt;
+  tp.gemm_fast = unit && cfast % 8 == 0;
+  // pipelined staging pays only on the dense path (measured: the gather
+  // path's extra register pressure under PIPE regressed l3.conv2 0.91->0.60)
+  tp.pipe = tp.gemm_fast && cp.K >= 4 * dwtmm::BK;
+  tp.swz = tp.gemm_fast && nt >= 8 && mt * nt >= 16;
+  return tp;
+}
+
+// ---- the direct-to-LDS switch ---------------------------------------------
 // The dense kernels take the direct-to-LDS loop where it applies unless this
 // is off (DWT_AMD_DENSE_GLDS=0 through dispatch, or set_dense_glds()).
 static bool g_dense_glds = true;
@@ -1465,79 +1506,78 @@ static inline bool aligned16(const Tensor& t) {
 // direct-to-LDS loop: whole k-steps (an LDS-DMA load cannot zero-fill), 16-byte
 // loads of both operands and 16-byte stores of the output.
 static inline bool dense_glds_ok(const Tensor& a, const Tensor& bt,
-                                 const Tensor& out, int64_t M, int64_t K,
-                                 int64_t N) {
-  return g_dense_glds && M > 0 && N > 0 && K > 0 && K % dwtmm::BK == 0 &&
-         N % 8 == 0 && aligned16(a) && aligned16(bt) && aligned16(out);
+                                 const Tensor& out,
+                                 const dwtmm::ConvParams& cp) {
+  return g_dense_glds && cp.K > 0 && cp.K % dwtmm::BK == 0 &&
+         cp.Cout % 8 == 0 && aligned16(a) && aligned16(bt) && aligned16(out);
 }
 
-// The direct-to-LDS instantiations of conv_implicit_gemm_kernel (PIPE unused).
-static void launch_dense_glds(const void* a, const void* bt, const float* bias,
-                              void* out, const dwtmm::ConvParams& cp,
-                              int mtiles, int ntiles, bool relu, bool has_bias,
-                              bool swz) {
-  auto launch = [&](auto reluc, auto biasc, auto swzc) {
+using ADense = std::integral_constant<int, dwtmm::A_DENSE>;
+using AConv = std::integral_constant<int, dwtmm::A_CONV>;
+using ADgrad = std::integral_constant<int, dwtmm::A_DGRAD>;
+constexpr std::false_type kOff{};
+
+// conv_implicit_gemm_kernel, instantiated for what tile_plan can select:
+//   A_DENSE x {RELU, BIAS, PIPE, SWZ}, and on the direct-to-LDS loop
+//   x {RELU, BIAS, SWZ};  A_CONV x {RELU, BIAS};  A_DGRAD.
+// mode is A_CONV / A_DGRAD for the gather; tp.gemm_fast overrides it.
+static void launch_conv_gemm(int mode, const Tensor& a, const Tensor& bt,
+                             const float* bias, const Tensor& out,
+                             const dwtmm::ConvParams& cp, const TilePlan& tp,
+                             bool relu) {
+  auto go = [&](auto modec, auto reluc, auto biasc, auto pipec, auto swzc,
+                auto gldsc) {
     hipLaunchKernelGGL(
-        (dwtmm::conv_implicit_gemm_kernel<dwtmm::A_DENSE,
-                                          decltype(reluc)::value,
-                                          decltype(biasc)::value, false,
-                                          decltype(swzc)::value, true>),
-        dim3(mtiles * ntiles), dim3(dwtmm::THREADS), 0, dwtmm_stream(),
-        (const c10::BFloat16*)a, (const c10::BFloat16*)bt, bias,
-        (c10::BFloat16*)out, cp, mtiles, ntiles);
+        (dwtmm::conv_implicit_gemm_kernel<
+            decltype(modec)::value, decltype(reluc)::value,
+            decltype(biasc)::value, decltype(pipec)::value,
+            decltype(swzc)::value, decltype(gldsc)::value>),
+        dim3(tp.mtiles * tp.ntiles), dim3(dwtmm::THREADS), 0, dwtmm_stream(),
+        (const c10::BFloat16*)a.data_ptr(), (const c10::BFloat16*)bt.data_ptr(),
+        bias, (c10::BFloat16*)out.data_ptr(), cp, tp.mtiles, tp.ntiles);
   };
-  auto pick_swz = [&](auto reluc, auto biasc) {
-    if (swz) launch(reluc, biasc, std::true_type{});
-    else launch(reluc, biasc, std::false_type{});
-  };
-  if (relu) { if (has_bias) pick_swz(std::true_type{}, std::true_type{});
-              else pick_swz(std::true_type{}, std::false_type{}); }
-  else { if (has_bias) pick_swz(std::false_type{}, std::true_type{});
-         else pick_swz(std::false_type{}, std::false_type{}); }
-  ++g_dense_glds_launches;
+  const bool has_bias = bias != nullptr;
+  if (tp.gemm_fast && dense_glds_ok(a, bt, out, cp)) {
+    static_dispatch(
+        [&](auto r, auto b, auto z) { go(ADense{}, r, b, kOff, z, std::true_type{}); },
+        relu, has_bias, tp.swz);
+    ++g_dense_glds_launches;
+  } else if (tp.gemm_fast) {
+    static_dispatch(
+        [&](auto r, auto b, auto p, auto z) { go(ADense{}, r, b, p, z, kOff); },
+        relu, has_bias, tp.pipe, tp.swz);
+  } else if (mode == dwtmm::A_CONV) {
+    static_dispatch(
+        [&](auto r, auto b) { go(AConv{}, r, b, kOff, kOff, kOff); }, relu,
+        has_bias);
+  } else {
+    TORCH_CHECK(mode == dwtmm::A_DGRAD && !relu && !has_bias,
+                "launch_conv_gemm: no such instantiation");
+    go(ADgrad{}, kOff, kOff, kOff, kOff, kOff);
+  }
+}
+
+static const float* bias_ptr(const char* who, const Tensor& bias,
+                             bool has_bias, int64_t n) {
+  if (!has_bias) return nullptr;
+  check_operands(who, {{"bias", bias, at::kFloat, n}});
+  return bias.data_ptr<float>();
 }
 
 // C[M,N] = A[M,K] @ Bt[N,K]^T (+bias +relu), all bf16, fp32 accumulate.
+// K % 8 == 0 (the A rows load 16 bytes at a time).
 void mfma_gemm(Tensor a, Tensor bt, Tensor bias, Tensor out, bool relu,
                bool has_bias) {
-  const int64_t M = a.size(0);
-  const int K = a.size(1);
-  const int N = bt.size(0);
-  TORCH_CHECK(bt.size(1) == K && out.size(0) == M && out.size(1) == N);
-  dwtmm::ConvParams cp{};
-  cp.M = M; cp.K = K; cp.Cout = N;
-  const int mtiles = (M + dwtmm::BM - 1) / dwtmm::BM;
-  const int ntiles = (N + dwtmm::BN - 1) / dwtmm::BN;
-  const bool pipe = K >= 4 * dwtmm::BK;
-  const bool swz = ntiles >= 8 && mtiles * ntiles >= 16;
-  if (dense_glds_ok(a, bt, out, M, K, N)) {
-    launch_dense_glds(a.data_ptr(), bt.data_ptr(),
-                      has_bias ? bias.data_ptr<float>() : nullptr,
-                      out.data_ptr(), cp, mtiles, ntiles, relu, has_bias, swz);
-    return;
-  }
-  auto run3 = [&](auto reluc, auto biasc, auto pipec, auto swzc) {
-    hipLaunchKernelGGL(
-        (dwtmm::conv_implicit_gemm_kernel<dwtmm::A_DENSE,
-                                          decltype(reluc)::value,
-                                          decltype(biasc)::value,
-                                          decltype(pipec)::value,
-                                          decltype(swzc)::value>),
-        dim3(mtiles * ntiles), dim3(dwtmm::THREADS), 0, dwtmm_stream(),
-        (const c10::BFloat16*)a.data_ptr(), (const c10::BFloat16*)bt.data_ptr(),
-        has_bias ? bias.data_ptr<float>() : nullptr,
-        (c10::BFloat16*)out.data_ptr(), cp, mtiles, ntiles);
-  };
-  auto run = [&](auto reluc, auto biasc) {
-    if (pipe) { if (swz) run3(reluc, biasc, std::true_type{}, std::true_type{});
-                else run3(reluc, biasc, std::true_type{}, std::false_type{}); }
-    else { if (swz) run3(reluc, biasc, std::false_type{}, std::true_type{});
-           else run3(reluc, biasc, std::false_type{}, std::false_type{}); }
-  };
-  if (relu) { if (has_bias) run(std::true_type{}, std::true_type{});
-              else run(std::true_type{}, std::false_type{}); }
-  else { if (has_bias) run(std::false_type{}, std::true_type{});
-         else run(std::false_type{}, std::false_type{}); }
+  const char* who = "mfma_gemm";
+  TORCH_CHECK(a.dim() == 2 && bt.dim() == 2, who, ": a and bt must be 2-D");
+  const int64_t M = a.size(0), K = a.size(1), N = bt.size(0);
+  TORCH_CHECK(bt.size(1) == K && K % 8 == 0, who, ": K = ", K);
+  check_operands(who, {{"a", a, at::kBFloat16, M * K},
+                       {"bt", bt, at::kBFloat16, N * K},
+                       {"out", out, at::kBFloat16, M * N}});
+  const dwtmm::ConvParams cp = gemm_params(who, M, K, N);
+  launch_conv_gemm(dwtmm::A_DENSE, a, bt, bias_ptr(who, bias, has_bias, N),
+                   out, cp, tile_plan(who, cp, true, K), relu);
 }
 
 // NHWC conv fwd: x (N,H,W,Cin) raw storage, wgt (Cout, KH*KW*Cin) raw
@@ -1547,54 +1587,14 @@ void mfma_conv2d_fwd(Tensor x, Tensor wgt, Tensor bias, Tensor out,
                      int64_t P, int64_t Q, int64_t Cout, int64_t KH,
                      int64_t KW, int64_t stride, int64_t pad, bool relu,
                      bool has_bias) {
-  dwtmm::ConvParams cp{};
-  cp.N = N; cp.H = H; cp.W = W; cp.Cin = Cin;
-  cp.P = P; cp.Q = Q; cp.Cout = Cout;
-  cp.KH = KH; cp.KW = KW; cp.stride = stride; cp.pad = pad;
-  cp.M = N * P * Q;
-  cp.K = KH * KW * Cin;
-  cp.cShift = log2_if_pow2(Cin);
-  const int mtiles = (cp.M + dwtmm::BM - 1) / dwtmm::BM;
-  const int ntiles = (Cout + dwtmm::BN - 1) / dwtmm::BN;
-  const bool gemm_fast = (KH == 1 && KW == 1 && stride == 1 && pad == 0 &&
-                          Cin % 8 == 0);
-  // pipelined staging pays only on the dense path (measured: the gather
-  // path's extra register pressure under PIPE regressed l3.conv2 0.91->0.60)
-  const bool pipe = gemm_fast && cp.K >= 4 * dwtmm::BK;
-  const bool swz = gemm_fast && ntiles >= 8 && mtiles * ntiles >= 16;
-  if (gemm_fast && dense_glds_ok(x, wgt, out, cp.M, cp.K, Cout)) {
-    launch_dense_glds(x.data_ptr(), wgt.data_ptr(),
-                      has_bias ? bias.data_ptr<float>() : nullptr,
-                      out.data_ptr(), cp, mtiles, ntiles, relu, has_bias, swz);
-    return;
-  }
-  auto run = [&](auto fastc, auto reluc, auto biasc) {
-    auto launch = [&](auto pipec, auto swzc) {
-      hipLaunchKernelGGL(
-          (dwtmm::conv_implicit_gemm_kernel<decltype(fastc)::value ? dwtmm::A_DENSE
-                                                                   : dwtmm::A_CONV,
-                                            decltype(reluc)::value,
-                                            decltype(biasc)::value,
-                                            decltype(pipec)::value,
-                                            decltype(swzc)::value>),
-          dim3(mtiles * ntiles), dim3(dwtmm::THREADS), 0, dwtmm_stream(),
-          (const c10::BFloat16*)x.data_ptr(), (const c10::BFloat16*)wgt.data_ptr(),
-          has_bias ? bias.data_ptr<float>() : nullptr,
-          (c10::BFloat16*)out.data_ptr(), cp, mtiles, ntiles);
-    };
-    if (pipe) { if (swz) launch(std::true_type{}, std::true_type{});
-                else launch(std::true_type{}, std::false_type{}); }
-    else { if (swz) launch(std::false_type{}, std::true_type{});
-           else launch(std::false_type{}, std::false_type{}); }
-  };
-  auto pick_rb = [&](auto fastc) {
-    if (relu) { if (has_bias) run(fastc, std::true_type{}, std::true_type{});
-                else run(fastc, std::true_type{}, std::false_type{}); }
-    else { if (has_bias) run(fastc, std::false_type{}, std::true_type{});
-           else run(fastc, std::false_type{}, std::false_type{}); }
-  };
-  if (gemm_fast) pick_rb(std::true_type{});
-  else pick_rb(std::false_type{});
+  const char* who = "mfma_conv2d_fwd";
+  const ConvGeom g{N, H, W, Cin, P, Q, Cout, KH, KW, stride, pad};
+  const dwtmm::ConvParams cp = conv_params(who, g, false);
+  check_operands(who, {{"x", x, at::kBFloat16, N * H * W * Cin},
+                       {"wgt", wgt, at::kBFloat16, Cout * cp.K},
+                       {"out", out, at::kBFloat16, cp.M * Cout}});
+  launch_conv_gemm(dwtmm::A_CONV, x, wgt, bias_ptr(who, bias, has_bias, Cout),
+                   out, cp, tile_plan(who, cp, g.unit(), Cin), relu);
 }
 
 // Folded-inference conv fwd: the kernel body, grid and PIPE / SWZ choices of
@@ -1608,67 +1608,40 @@ void mfma_conv2d_fwd_fused(Tensor x, Tensor wgt, Tensor bias, Tensor res,
                            int64_t Cin, int64_t P, int64_t Q, int64_t Cout,
                            int64_t KH, int64_t KW, int64_t stride, int64_t pad,
                            bool relu, bool has_res) {
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 &&
-              wgt.scalar_type() == at::kBFloat16 &&
-              out.scalar_type() == at::kBFloat16 &&
-              bias.scalar_type() == at::kFloat, "mfma_conv2d_fwd_fused: dtypes");
-  TORCH_CHECK(x.is_cuda() && wgt.is_cuda() && bias.is_cuda() && out.is_cuda());
-  TORCH_CHECK(Cout % 8 == 0, "mfma_conv2d_fwd_fused: Cout % 8");
-  TORCH_CHECK(x.numel() == N * H * W * Cin && wgt.numel() == Cout * KH * KW * Cin &&
-              bias.numel() == Cout && out.numel() == N * P * Q * Cout,
-              "mfma_conv2d_fwd_fused: sizes");
+  const char* who = "mfma_conv2d_fwd_fused";
+  const ConvGeom g{N, H, W, Cin, P, Q, Cout, KH, KW, stride, pad};
+  const dwtmm::ConvParams cp = conv_params(who, g, false);
+  check_operands(who, {{"x", x, at::kBFloat16, N * H * W * Cin},
+                       {"wgt", wgt, at::kBFloat16, Cout * cp.K},
+                       {"bias", bias, at::kFloat, Cout},
+                       {"out", out, at::kBFloat16, cp.M * Cout}});
+  if (has_res) check_operands(who, {{"res", res, at::kBFloat16, cp.M * Cout}});
+  TORCH_CHECK(Cout % 8 == 0, who, ": Cout % 8");
   TORCH_CHECK(P == (H + 2 * pad - KH) / stride + 1 &&
-              Q == (W + 2 * pad - KW) / stride + 1,
-              "mfma_conv2d_fwd_fused: output extent");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0,
-              "mfma_conv2d_fwd_fused: out alignment");
-  if (has_res) {
-    TORCH_CHECK(res.is_cuda() && res.scalar_type() == at::kBFloat16 &&
-                res.numel() == out.numel() &&
-                reinterpret_cast<uintptr_t>(res.data_ptr()) % 16 == 0,
-                "mfma_conv2d_fwd_fused: res");
-  }
-  dwtmm::ConvParams cp{};
-  cp.N = N; cp.H = H; cp.W = W; cp.Cin = Cin;
-  cp.P = P; cp.Q = Q; cp.Cout = Cout;
-  cp.KH = KH; cp.KW = KW; cp.stride = stride; cp.pad = pad;
-  cp.M = N * P * Q;
-  cp.K = KH * KW * Cin;
-  cp.cShift = log2_if_pow2(Cin);
-  const int64_t mt64 = (cp.M + dwtmm::BM - 1) / dwtmm::BM;
-  const int ntiles = (Cout + dwtmm::BN - 1) / dwtmm::BN;
-  TORCH_CHECK(cp.M > 0 && mt64 * ntiles < (int64_t)1 << 31);
-  const int mtiles = (int)mt64;
-  const bool gemm_fast = (KH == 1 && KW == 1 && stride == 1 && pad == 0 &&
-                          Cin % 8 == 0);
-  const bool pipe = gemm_fast && cp.K >= 4 * dwtmm::BK;
-  const bool swz = gemm_fast && ntiles >= 8 && mtiles * ntiles >= 16;
-  auto launch = [&](auto modec, auto reluc, auto resc, auto pipec, auto swzc) {
+              Q == (W + 2 * pad - KW) / stride + 1, who, ": output extent");
+  TORCH_CHECK(aligned16(out) && (!has_res || aligned16(res)), who,
+              ": out / res alignment");
+  const TilePlan tp = tile_plan(who, cp, g.unit(), Cin);
+  auto go = [&](auto modec, auto reluc, auto resc, auto pipec, auto swzc) {
     hipLaunchKernelGGL(
         (dwtmm::conv_fused_fwd_kernel<decltype(modec)::value,
                                       decltype(reluc)::value,
                                       decltype(resc)::value,
                                       decltype(pipec)::value,
                                       decltype(swzc)::value>),
-        dim3(mtiles * ntiles), dim3(dwtmm::THREADS), 0, dwtmm_stream(),
+        dim3(tp.mtiles * tp.ntiles), dim3(dwtmm::THREADS), 0, dwtmm_stream(),
         (const c10::BFloat16*)x.data_ptr(), (const c10::BFloat16*)wgt.data_ptr(),
         bias.data_ptr<float>(),
         has_res ? (const c10::BFloat16*)res.data_ptr() : nullptr,
-        (c10::BFloat16*)out.data_ptr(), cp, mtiles, ntiles);
+        (c10::BFloat16*)out.data_ptr(), cp, tp.mtiles, tp.ntiles);
   };
-  using DEN = std::integral_constant<int, dwtmm::A_DENSE>;
-  using CNV = std::integral_constant<int, dwtmm::A_CONV>;
-  auto pick_mode = [&](auto reluc, auto resc) {
-    if (!gemm_fast) { launch(CNV{}, reluc, resc, std::false_type{}, std::false_type{}); return; }
-    if (pipe) { if (swz) launch(DEN{}, reluc, resc, std::true_type{}, std::true_type{});
-                else launch(DEN{}, reluc, resc, std::true_type{}, std::false_type{}); }
-    else { if (swz) launch(DEN{}, reluc, resc, std::false_type{}, std::true_type{});
-           else launch(DEN{}, reluc, resc, std::false_type{}, std::false_type{}); }
-  };
-  if (relu) { if (has_res) pick_mode(std::true_type{}, std::true_type{});
-              else pick_mode(std::true_type{}, std::false_type{}); }
-  else { if (has_res) pick_mode(std::false_type{}, std::true_type{});
-         else pick_mode(std::false_type{}, std::false_type{}); }
+  if (tp.gemm_fast)
+    static_dispatch(
+        [&](auto r, auto s, auto p, auto z) { go(ADense{}, r, s, p, z); }, relu,
+        has_res, tp.pipe, tp.swz);
+  else
+    static_dispatch([&](auto r, auto s) { go(AConv{}, r, s, kOff, kOff); },
+                    relu, has_res);
 }
 
 
@@ -1680,77 +1653,56 @@ void mfma_conv2d_fwd_fused(Tensor x, Tensor wgt, Tensor bias, Tensor res,
 // workgroups for this device; tests pass 1 or 2 to force long runs.
 void conv1x1_stats(Tensor x, Tensor wgt, Tensor out, Tensor acc, int64_t kind,
                    int64_t g, int64_t parts, int64_t max_workgroups) {
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 &&
-              wgt.scalar_type() == at::kBFloat16 &&
-              out.scalar_type() == at::kBFloat16 &&
-              acc.scalar_type() == at::kFloat, "conv1x1_stats: dtypes");
-  TORCH_CHECK(x.is_cuda() && wgt.is_cuda() && out.is_cuda() && acc.is_cuda());
-  TORCH_CHECK(wgt.dim() >= 2 && acc.is_contiguous());
+  const char* who = "conv1x1_stats";
+  TORCH_CHECK(wgt.dim() >= 2 && wgt.size(0) > 0 && wgt.numel() > 0 &&
+              acc.is_contiguous(), who, ": wgt / acc layout");
   const int64_t Cout = wgt.size(0);
   const int64_t Cin = wgt.numel() / Cout;
-  TORCH_CHECK(Cin % 8 == 0 && Cout % 8 == 0, "conv1x1_stats: C % 8");
-  TORCH_CHECK(x.numel() % Cin == 0);
+  TORCH_CHECK(Cin % 8 == 0 && Cout % 8 == 0, who, ": C % 8");
+  TORCH_CHECK(x.numel() % Cin == 0, who, ": x size");
   const int64_t M = x.numel() / Cin;
-  TORCH_CHECK(out.numel() == M * Cout);
   TORCH_CHECK(parts >= 1 && M % parts == 0 && (M / parts) % dwtmm::BM == 0,
-              "conv1x1_stats: rows per branch must be a multiple of ",
-              dwtmm::BM);
+              who, ": rows per branch must be a multiple of ", dwtmm::BM);
   TORCH_CHECK(kind == dwtmm::STATS_BN || (kind == dwtmm::STATS_WHITEN4 && g == 4),
-              "conv1x1_stats: BN or whitening with g = 4 only");
-  const int64_t acc_n = kind == dwtmm::STATS_BN ? parts * 2 * Cout
-                                                : parts * (Cout / 4) * 20;
-  TORCH_CHECK(acc.numel() == acc_n, "conv1x1_stats: acc size");
-  TORCH_CHECK(M / dwtmm::BM < (int64_t)1 << 31);
-
-  dwtmm::ConvParams cp{};
-  cp.M = M; cp.K = (int)Cin; cp.Cout = (int)Cout;
-  const int mtiles = (int)(M / dwtmm::BM);
-  const int ntiles = (int)((Cout + dwtmm::BN - 1) / dwtmm::BN);
-  const bool pipe = cp.K >= 4 * dwtmm::BK;
-  const bool glds = dense_glds_ok(x, wgt, out, M, Cin, Cout);
+              who, ": BN or whitening with g = 4 only");
+  check_operands(who, {{"x", x, at::kBFloat16, M * Cin},
+                       {"wgt", wgt, at::kBFloat16, Cout * Cin},
+                       {"out", out, at::kBFloat16, M * Cout},
+                       {"acc", acc, at::kFloat,
+                        kind == dwtmm::STATS_BN ? parts * 2 * Cout
+                                                : parts * (Cout / 4) * 20}});
+  const dwtmm::ConvParams cp = gemm_params(who, M, Cin, Cout);
+  const TilePlan tp = tile_plan(who, cp, true, Cin);
+  const bool glds = dense_glds_ok(x, wgt, out, cp);
   int64_t maxwg = max_workgroups;
   if (maxwg <= 0) {
     // queried once: the CU count of whichever device is current on the
     // first call serves every device (the supported boxes are homogeneous)
     static const int cus =
         at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
-    maxwg = (int64_t)cus * ((pipe || glds) ? 2 : 3);
+    maxwg = (int64_t)cus * ((tp.pipe || glds) ? 2 : 3);
   }
-  const int nlanes = (int)std::min<int64_t>(maxwg, ntiles);
+  const int nlanes = (int)std::min<int64_t>(maxwg, tp.ntiles);
   const int runs = (int)std::max<int64_t>(
-      1, std::min<int64_t>(maxwg / nlanes, mtiles));
-  auto launch = [&](auto pipec, auto kindc) {
+      1, std::min<int64_t>(maxwg / nlanes, tp.mtiles));
+  // both kernels take the same arguments
+  auto launch = [&](auto kernel) {
     hipLaunchKernelGGL(
-        (dwtmm::conv1x1_stats_kernel<decltype(pipec)::value,
-                                     decltype(kindc)::value>),
-        dim3(nlanes * runs), dim3(dwtmm::THREADS), 0, dwtmm_stream(),
+        kernel, dim3(nlanes * runs), dim3(dwtmm::THREADS), 0, dwtmm_stream(),
         (const c10::BFloat16*)x.data_ptr(), (const c10::BFloat16*)wgt.data_ptr(),
-        (c10::BFloat16*)out.data_ptr(), acc.data_ptr<float>(), cp, mtiles,
-        ntiles, (int)(M / parts / dwtmm::BM), nlanes, runs);
+        (c10::BFloat16*)out.data_ptr(), acc.data_ptr<float>(), cp, tp.mtiles,
+        tp.ntiles, (int)(M / parts / dwtmm::BM), nlanes, runs);
   };
-  using KBN = std::integral_constant<int, dwtmm::STATS_BN>;
-  using KWH = std::integral_constant<int, dwtmm::STATS_WHITEN4>;
+  const OneOf<dwtmm::STATS_BN, dwtmm::STATS_WHITEN4> kinds{kind};
   if (glds) {
-    auto launch_glds = [&](auto kindc) {
-      hipLaunchKernelGGL(
-          (dwtmm::conv1x1_stats_glds_kernel<decltype(kindc)::value>),
-          dim3(nlanes * runs), dim3(dwtmm::THREADS), 0, dwtmm_stream(),
-          (const c10::BFloat16*)x.data_ptr(),
-          (const c10::BFloat16*)wgt.data_ptr(), (c10::BFloat16*)out.data_ptr(),
-          acc.data_ptr<float>(), cp, mtiles, ntiles,
-          (int)(M / parts / dwtmm::BM), nlanes, runs);
-    };
-    if (kind == dwtmm::STATS_BN) launch_glds(KBN{});
-    else launch_glds(KWH{});
+    static_dispatch([&](auto k) {
+      launch(dwtmm::conv1x1_stats_glds_kernel<decltype(k)::value>);
+    }, kinds);
     ++g_dense_glds_launches;
-    return;
-  }
-  if (kind == dwtmm::STATS_BN) {
-    if (pipe) launch(std::true_type{}, KBN{});
-    else launch(std::false_type{}, KBN{});
   } else {
-    if (pipe) launch(std::true_type{}, KWH{});
-    else launch(std::false_type{}, KWH{});
+    static_dispatch([&](auto p, auto k) {
+      launch(dwtmm::conv1x1_stats_kernel<decltype(p)::value, decltype(k)::value>);
+    }, tp.pipe, kinds);
   }
 }
 
@@ -1761,125 +1713,99 @@ void mfma_conv2d_dgrad(Tensor dy, Tensor wd, Tensor dx, int64_t N, int64_t H,
                        int64_t W, int64_t Cin, int64_t P, int64_t Q,
                        int64_t Cdy, int64_t KH, int64_t KW, int64_t stride,
                        int64_t pad) {
-  dwtmm::ConvParams cp{};
-  cp.N = N; cp.H = H; cp.W = W; cp.Cin = Cin;
-  cp.P = P; cp.Q = Q; cp.Cout = Cin;  // GEMM output channels = Cin
-  cp.KH = KH; cp.KW = KW; cp.stride = stride; cp.pad = pad;
-  cp.Cdy = Cdy;
-  cp.M = N * H * W;
-  cp.K = KH * KW * Cdy;
-  cp.cShift = log2_if_pow2(Cdy);
-  const int mtiles = (cp.M + dwtmm::BM - 1) / dwtmm::BM;
-  const int ntiles = (Cin + dwtmm::BN - 1) / dwtmm::BN;
-  // 1x1/stride-1 dgrad IS the dense GEMM dy @ w^T — run it on the
+  const char* who = "mfma_conv2d_dgrad";
+  const ConvGeom g{N, H, W, Cin, P, Q, Cdy, KH, KW, stride, pad};
+  const dwtmm::ConvParams cp = conv_params(who, g, true);
+  check_operands(who, {{"dy", dy, at::kBFloat16, N * P * Q * Cdy},
+                       {"wd", wd, at::kBFloat16, Cin * cp.K},
+                       {"dx", dx, at::kBFloat16, cp.M * Cin}});
+  // 1x1/stride-1 dgrad IS the dense GEMM dy @ w^T — tile_plan puts it on the
   // pipelined/swizzled dense path instead of the per-chunk gather decode
-  const bool gemm_fast = (KH == 1 && KW == 1 && stride == 1 && pad == 0 &&
-                          Cdy % 8 == 0);
-  const bool pipe = gemm_fast && cp.K >= 4 * dwtmm::BK;
-  const bool swz = gemm_fast && ntiles >= 8 && mtiles * ntiles >= 16;
-  auto launch = [&](auto modec, auto pipec, auto swzc) {
-    hipLaunchKernelGGL(
-        (dwtmm::conv_implicit_gemm_kernel<decltype(modec)::value,
-                                          false, false,
-                                          decltype(pipec)::value,
-                                          decltype(swzc)::value>),
-        dim3(mtiles * ntiles), dim3(dwtmm::THREADS), 0, dwtmm_stream(),
-        (const c10::BFloat16*)dy.data_ptr(), (const c10::BFloat16*)wd.data_ptr(),
-        nullptr, (c10::BFloat16*)dx.data_ptr(), cp, mtiles, ntiles);
-  };
-  using DEN = std::integral_constant<int, dwtmm::A_DENSE>;
-  using DGR = std::integral_constant<int, dwtmm::A_DGRAD>;
-  if (gemm_fast && dense_glds_ok(dy, wd, dx, cp.M, cp.K, Cin)) {
-    launch_dense_glds(dy.data_ptr(), wd.data_ptr(), nullptr, dx.data_ptr(), cp,
-                      mtiles, ntiles, false, false, swz);
-  } else if (gemm_fast) {
-    if (pipe) { if (swz) launch(DEN{}, std::true_type{}, std::true_type{});
-                else launch(DEN{}, std::true_type{}, std::false_type{}); }
-    else { if (swz) launch(DEN{}, std::false_type{}, std::true_type{});
-           else launch(DEN{}, std::false_type{}, std::false_type{}); }
-  } else if (stride > 1 && log2_if_pow2(Cdy) >= 0 && Cdy >= 8) {
-    // class decomposition: one launch per (h%stride, w%stride) residue
-    for (int ch = 0; ch < stride; ++ch) {
-      for (int cw = 0; cw < stride; ++cw) {
-        dwtmm::DgradClsParams gp{};
-        gp.H = H; gp.W = W; gp.Cin = Cin; gp.P = P; gp.Q = Q;
-        gp.Cdy = Cdy; gp.Kfull = KH * KW * Cdy;
-        gp.ch = ch; gp.cw = cw; gp.stride = stride;
-        gp.Hc = (int)((H - ch + stride - 1) / stride);
-        gp.Wc = (int)((W - cw + stride - 1) / stride);
-        gp.M = (int64_t)N * gp.Hc * gp.Wc;
-        gp.cShift = log2_if_pow2(Cdy);
-        int rl[16], sl[16], nr = 0, ns = 0;
-        for (int r = 0; r < KH; ++r)
-          if ((ch + pad - r) % stride == 0 && nr < 4) rl[nr++] = r;
-        for (int s = 0; s < KW; ++s)
-          if ((cw + pad - s) % stride == 0 && ns < 4) sl[ns++] = s;
-        int ntaps = 0;
-        for (int a = 0; a < nr && ntaps < 16; ++a)
-          for (int b = 0; b < ns && ntaps < 16; ++b) {
-            gp.dp[ntaps] = (int)((ch + pad - rl[a]) / stride);
-            gp.dq[ntaps] = (int)((cw + pad - sl[b]) / stride);
-            gp.rsIdx[ntaps] = rl[a] * KW + sl[b];
-            ++ntaps;
-          }
-        gp.K = ntaps * Cdy;
-        if (ntaps == 0 || gp.M == 0) continue;
-        const int cm = (int)((gp.M + dwtmm::BM - 1) / dwtmm::BM);
-        hipLaunchKernelGGL(dwtmm::dgrad_cls_kernel, dim3(cm * ntiles),
-                           dim3(dwtmm::THREADS), 0, dwtmm_stream(),
-                           (const c10::BFloat16*)dy.data_ptr(),
-                           (const c10::BFloat16*)wd.data_ptr(),
-                           (c10::BFloat16*)dx.data_ptr(), gp, cm, ntiles);
-      }
+  const TilePlan tp = tile_plan(who, cp, g.unit(), Cdy);
+  if (tp.gemm_fast || stride == 1 || cp.cShift < 0 || Cdy < 8) {
+    launch_conv_gemm(dwtmm::A_DGRAD, dy, wd, nullptr, dx, cp, tp, false);
+    return;
+  }
+  // class decomposition: one launch per (h%stride, w%stride) residue
+  for (int ch = 0; ch < stride; ++ch) {
+    for (int cw = 0; cw < stride; ++cw) {
+      dwtmm::DgradClsParams gp{};
+      gp.H = H; gp.W = W; gp.Cin = Cin; gp.P = P; gp.Q = Q;
+      gp.Cdy = Cdy; gp.Kfull = cp.K;
+      gp.ch = ch; gp.cw = cw; gp.stride = stride;
+      gp.Hc = (int)((H - ch + stride - 1) / stride);
+      gp.Wc = (int)((W - cw + stride - 1) / stride);
+      gp.M = (int64_t)N * gp.Hc * gp.Wc;
+      gp.cShift = cp.cShift;
+      int rl[16], sl[16], nr = 0, ns = 0;
+      for (int r = 0; r < KH; ++r)
+        if ((ch + pad - r) % stride == 0 && nr < 4) rl[nr++] = r;
+      for (int s = 0; s < KW; ++s)
+        if ((cw + pad - s) % stride == 0 && ns < 4) sl[ns++] = s;
+      int ntaps = 0;
+      for (int a = 0; a < nr && ntaps < 16; ++a)
+        for (int b = 0; b < ns && ntaps < 16; ++b) {
+          gp.dp[ntaps] = (int)((ch + pad - rl[a]) / stride);
+          gp.dq[ntaps] = (int)((cw + pad - sl[b]) / stride);
+          gp.rsIdx[ntaps] = rl[a] * KW + sl[b];
+          ++ntaps;
+        }
+      gp.K = ntaps * Cdy;
+      if (ntaps == 0 || gp.M == 0) continue;
+      // gp.M <= cp.M: the class grid fits wherever the plan's does
+      const int cm = (int)((gp.M + dwtmm::BM - 1) / dwtmm::BM);
+      hipLaunchKernelGGL(dwtmm::dgrad_cls_kernel, dim3(cm * tp.ntiles),
+                         dim3(dwtmm::THREADS), 0, dwtmm_stream(),
+                         (const c10::BFloat16*)dy.data_ptr(),
+                         (const c10::BFloat16*)wd.data_ptr(),
+                         (c10::BFloat16*)dx.data_ptr(), gp, cm, tp.ntiles);
     }
-  } else {
-    if (pipe) launch(DGR{}, std::true_type{}, std::false_type{});
-    else launch(DGR{}, std::false_type{}, std::false_type{});
   }
 }
 
 
 // wgrad v2 (split-K): dy (N,P,Q,Cout) raw NHWC, x (N,H,W,Cin) raw NHWC,
 // ws fp32 zero-initialized [Cout, KH*KW*Cin], dw bf16 channels_last weight
-// storage (same [co][r][s][ci] flat layout as ws).
+// storage (same [co][r][s][ci] flat layout as ws).  Cout % 8 == 0 (the dy
+// tile loads 16 bytes at a time).
 // ConvParams reuse here: cp.N = Cout (dy channel stride), cp.Cout =
 // KH*KW*Cin (dw columns), cp.M = real NPQ.
 void mfma_conv2d_wgrad(Tensor dy, Tensor x, Tensor dw, Tensor ws, int64_t N,
                        int64_t H, int64_t W, int64_t Cin, int64_t P,
                        int64_t Q, int64_t Cout, int64_t KH, int64_t KW,
                        int64_t stride, int64_t pad) {
-  dwtmm::ConvParams cp{};
-  cp.N = Cout; cp.H = H; cp.W = W; cp.Cin = Cin;
-  cp.P = P; cp.Q = Q;
-  cp.KH = KH; cp.KW = KW; cp.stride = stride; cp.pad = pad;
-  cp.M = (int64_t)N * P * Q;
-  cp.Cout = KH * KW * Cin;
+  const char* who = "mfma_conv2d_wgrad";
+  const ConvGeom g{N, H, W, Cin, P, Q, Cout, KH, KW, stride, pad};
+  dwtmm::ConvParams cp = conv_params(who, g, false);
+  const int64_t n = (int64_t)Cout * cp.K;      // elements of dw
+  check_operands(who, {{"dy", dy, at::kBFloat16, cp.M * Cout},
+                       {"x", x, at::kBFloat16, N * H * W * Cin},
+                       {"dw", dw, at::kBFloat16, n},
+                       {"ws", ws, at::kFloat, n}});
+  TORCH_CHECK(Cout % 8 == 0, who, ": Cout % 8");
+  cp.N = Cout;
+  cp.Cout = cp.K;
   // 128 tile when both dims fill it (4x less cross-tile operand traffic);
   // 64 tile otherwise (stem/l1 shapes would waste half the MFMA work)
   const int WT = (Cout >= 128 && cp.Cout >= 128) ? 128 : 64;
   const int mtiles = (int)((Cout + WT - 1) / WT);
   const int ntiles = (cp.Cout + WT - 1) / WT;
+  TORCH_CHECK((int64_t)mtiles * ntiles < (int64_t)1 << 31 &&
+              (n + 255) / 256 < (int64_t)1 << 31, who,
+              ": grid does not fit 32 bits");
   // split K so the grid lands at >=2048 workgroups (256 CUs, several waves
   // deep), k-slabs rounded to whole BK tiles
   int64_t splitk = std::max<int64_t>(1, 2048 / (mtiles * ntiles));
   const int64_t kt = (cp.M + dwtmm::WBK - 1) / dwtmm::WBK;  // total k-tiles
   splitk = std::min<int64_t>(splitk, kt);
   const int64_t klen = ((kt + splitk - 1) / splitk) * dwtmm::WBK;
-  const bool aligned = (Cin % 64 == 0);
-  auto launch = [&](auto ac, auto wtc) {
+  static_dispatch([&](auto ac, auto wtc) {
     hipLaunchKernelGGL(
         (dwtmm::wgrad_splitk_kernel<decltype(ac)::value, decltype(wtc)::value>),
         dim3(mtiles * ntiles * splitk), dim3(256), 0, dwtmm_stream(),
         (const c10::BFloat16*)dy.data_ptr(), (const c10::BFloat16*)x.data_ptr(),
         ws.data_ptr<float>(), cp, mtiles, ntiles, (int)splitk, klen);
-  };
-  using T64 = std::integral_constant<int, 64>;
-  using T128 = std::integral_constant<int, 128>;
-  if (aligned) { if (WT == 128) launch(std::true_type{}, T128{});
-                 else launch(std::true_type{}, T64{}); }
-  else { if (WT == 128) launch(std::false_type{}, T128{});
-         else launch(std::false_type{}, T64{}); }
-  const int64_t n = (int64_t)Cout * cp.Cout;
+  }, Cin % 64 == 0, OneOf<64, 128>{WT});
   hipLaunchKernelGGL(dwtmm::f32_to_bf16_kernel, dim3((n + 255) / 256),
                      dim3(256), 0, dwtmm_stream(), ws.data_ptr<float>(),
                      (c10::BFloat16*)dw.data_ptr(), n);

@@ -117,8 +117,6 @@ def conv2d_fwd(x: torch.Tensor, weight: torch.Tensor,
         wgt = wgt.contiguous(memory_format=torch.channels_last)
     has_bias = bias is not None
     b32 = bias.detach().float().contiguous() if has_bias else torch.empty(0, device=x.device)
-    if (kh * kw * cin) % 8 != 0 and not (kh == 1 and kw == 1 and stride == 1 and padding == 0):
-        pass  # slow per-element gather path inside the kernel handles it
     _ext().mfma_conv2d_fwd(x, wgt, b32, out, n, h, w, cin, p, q, cout,
                            kh, kw, stride, padding, relu, has_bias)
     return out

@@ -8,6 +8,8 @@ import torch
 import torch.nn.functional as F
 from torch.utils.data import DataLoader
 
+from exact_cases import exact_case as _shared_exact_case, out_hw
+
 pytestmark = pytest.mark.gpu
 
 BF16 = torch.bfloat16
@@ -39,32 +41,13 @@ def _cl(t):
 
 
 def _out_hw(shape):
-    n, cin, h, w, cout, k, s, p = shape
-    return (h + 2 * p - k) // s + 1, (w + 2 * p - k) // s + 1
-
-
-_EXACT = {}
+    return out_hw(shape)
 
 
 def exact_case(shape):
-    """Integer-valued inputs (exact in bf16, every partial sum an exact fp32
-    integer whatever the accumulation order) and the fp32 conv of them, drawn
-    once per shape on the CPU with a fixed seed and left unchanged."""
-    if shape in _EXACT:
-        return _EXACT[shape]
-    n, cin, h, w, cout, k, s, p = shape
-    gen = torch.Generator().manual_seed(1234 + SHAPES.index(shape))
-    ph, pw = _out_hw(shape)
-    x = torch.randint(0, 4, (n, cin, h, w), generator=gen).float()
-    wt = torch.randint(-2, 3, (cout, cin, k, k), generator=gen).float()
-    bias = torch.randint(-8, 9, (cout,), generator=gen).float() * 0.25
-    res = torch.randint(-16, 17, (n, cout, ph, pw), generator=gen).float() * 0.25
-    conv = F.conv2d(x, wt, None, s, p)
-    conv64 = F.conv2d(x.double(), wt.double(), None, s, p)
-    assert torch.equal(conv.double(), conv64), "fp32 reference is not exact"
-    case = dict(x=x, w=wt, bias=bias, res=res, conv=conv)
-    _EXACT[shape] = case
-    return case
+    """The shared integer-valued case of this shape (tests/exact_cases.py),
+    one fixed seed per shape."""
+    return _shared_exact_case(shape, 1234 + SHAPES.index(shape))
 
 
 def expected(case, relu, with_res):
