@@ -1,7 +1,7 @@
 """In-tree build of the gfx950 HIP extension.
 
-Usage: ``python -m dwt_amd.kernels.build``.  Compiles every
-``src/*.hip`` + ``src/bindings.cpp`` into ``dwt_amd/kernels/_dwt_hip.so``
+Usage: ``python -m dwt_amd.kernels.build``.  Compiles every ``src/*.hip``
+(the bindings are in them) into ``dwt_amd/kernels/_dwt_hip.so``
 (the .so travels to the GPU box with the repo snapshot; a JIT cache under
 ~/.cache would not).  hipcc cross-compiles on a CPU-only box.
 """

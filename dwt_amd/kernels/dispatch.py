@@ -75,14 +75,18 @@ def require_or_warn(opname: str) -> None:
 # The concrete HIP-backed implementations are registered here once the
 # extension exists; ops import these names.
 
-def whiten_multi(x, gamma, beta, running_means, running_vars, cfg):
+def whiten_multi(x, gamma, beta, running_means, running_vars, cfg,
+                 stats_acc=None):
     from . import hip_ops
-    return hip_ops.whiten_multi(x, gamma, beta, running_means, running_vars, cfg)
+    return hip_ops.whiten_multi(x, gamma, beta, running_means, running_vars,
+                                cfg, stats_acc)
 
 
-def batch_norm_multi(x, gamma, beta, running_means, running_vars, cfg):
+def batch_norm_multi(x, gamma, beta, running_means, running_vars, cfg,
+                     stats_acc=None):
     from . import hip_ops
-    return hip_ops.batch_norm_multi(x, gamma, beta, running_means, running_vars, cfg)
+    return hip_ops.batch_norm_multi(x, gamma, beta, running_means,
+                                    running_vars, cfg, stats_acc)
 
 
 def mec_loss(x, y):

@@ -49,7 +49,7 @@ def whiten_cl_supported(c, g):
     return False
 
 
-def _bn_cl_supported(c):
+def bn_cl_supported(c):
     """The NHWC BN kernels map lanes as t %% NCH with NCH = min(C,1024)/4;
     rows advance by blockDim/NCH — NCH must divide the block (else boundary
     rows are double-counted)."""
@@ -60,10 +60,10 @@ def _bn_cl_supported(c):
 
 
 def _bn_layout(x, c):
-    if x.dim() == 2 and x.is_contiguous() and _bn_cl_supported(c):
+    if x.dim() == 2 and x.is_contiguous() and bn_cl_supported(c):
         return "cl"  # (N, C) IS channels-last: C contiguous per position
     if x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last) \
-            and not x.is_contiguous() and _bn_cl_supported(c):
+            and not x.is_contiguous() and bn_cl_supported(c):
         return "cl"
     return "nchw"
 
@@ -135,12 +135,11 @@ class _HipWhitenMulti(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, running_means, running_vars, cfg,
-                res=None):
+                stats_acc=None, res=None):
+        # stats_acc: see _usable_stats_acc
         # res (channels_last layout only; passed by _HipWhitenJoin, never
         # through apply): the apply pass writes relu(norm(x) + res)
         ext = _ext()
-        # taken out of cfg here, used or not: ctx.cfg keeps no tensor
-        stats_acc = cfg.pop("stats_acc", None)
         parts = cfg["parts"]
         g = x.shape[1] // cfg["num_groups"]
         eps, momentum = cfg["eps"], cfg["momentum"]
@@ -238,7 +237,7 @@ class _HipWhitenMulti(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         dx, _, dgamma, dbeta = _HipWhitenMulti.run_backward(ctx, dout)
-        return dx, dgamma, dbeta, None, None, None
+        return dx, dgamma, dbeta, None, None, None, None
 
     @staticmethod
     def run_backward(ctx, dout, gb=None, join=False):
@@ -350,35 +349,38 @@ def join_supported(kind, x, identity, cfg):
     return _bn_layout(x, c) == "cl"
 
 
-def whiten_join(x, identity, gamma, beta, running_means, running_vars, cfg):
+def whiten_join(x, identity, gamma, beta, running_means, running_vars, cfg,
+                stats_acc=None):
     return _HipWhitenJoin.apply(x, identity, gamma, beta, running_means,
-                                running_vars, cfg)
+                                running_vars, cfg, stats_acc)
 
 
-def batch_norm_join(x, identity, gamma, beta, running_means, running_vars, cfg):
+def batch_norm_join(x, identity, gamma, beta, running_means, running_vars, cfg,
+                    stats_acc=None):
     return _HipBatchNormJoin.apply(x, identity, gamma, beta, running_means,
-                                   running_vars, cfg)
+                                   running_vars, cfg, stats_acc)
 
 
-def whiten_multi(x, gamma, beta, running_means, running_vars, cfg):
+def whiten_multi(x, gamma, beta, running_means, running_vars, cfg,
+                 stats_acc=None):
     g = x.shape[1] // cfg["num_groups"]
     if g > _GEN_G_MAX or x.dtype not in (torch.float32, torch.bfloat16):
         _warn_once(("wh", g, x.dtype),
                    f"dwt_amd: whiten_multi g={g} dtype={x.dtype} uses the "
                    "torch path (HIP kernels cover g <= 32, fp32/bf16)")
         from ..ops.functional import WhitenMulti
-        cfg.pop("stats_acc", None)  # the torch path takes its own statistics
+        # the torch path takes its own statistics
         return WhitenMulti.apply(x, gamma, beta, running_means, running_vars, cfg)
-    return _HipWhitenMulti.apply(x, gamma, beta, running_means, running_vars, cfg)
+    return _HipWhitenMulti.apply(x, gamma, beta, running_means, running_vars,
+                                 cfg, stats_acc)
 
 
 class _HipBatchNormMulti(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, running_means, running_vars, cfg,
-                res=None):
-        # res: as in _HipWhitenMulti.forward
+                stats_acc=None, res=None):
+        # stats_acc, res: as in _HipWhitenMulti.forward
         ext = _ext()
-        stats_acc = cfg.pop("stats_acc", None)  # as in _HipWhitenMulti
         parts = cfg["parts"]
         eps, momentum = cfg["eps"], cfg["momentum"]
         training, relu = cfg["training"], cfg["relu"]
@@ -460,7 +462,7 @@ class _HipBatchNormMulti(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         dx, _, dgamma, dbeta = _HipBatchNormMulti.run_backward(ctx, dout)
-        return dx, dgamma, dbeta, None, None, None
+        return dx, dgamma, dbeta, None, None, None, None
 
     @staticmethod
     def run_backward(ctx, dout, gb=None, join=False):
@@ -532,20 +534,20 @@ def _join_function(name, site):
     the join reduce kernel — autograd never runs its accumulation kernel."""
 
     def forward(ctx, x, identity, gamma, beta, running_means, running_vars,
-                cfg):
+                cfg, stats_acc=None):
         ctx.set_materialize_grads(False)
         res = identity.detach()  # channels_last: join_supported checked it
         y = site.forward(ctx, x, gamma, beta, running_means, running_vars,
-                         cfg, res=res)
+                         cfg, stats_acc, res=res)
         return y, y.view_as(y)
 
     def backward(ctx, ga, gb):
         if ga is None and gb is None:
-            return (None,) * 7
+            return (None,) * 8
         if ga is None:
             ga, gb = gb, None
         dx, gid, dgamma, dbeta = site.run_backward(ctx, ga, gb, join=True)
-        return dx, gid, dgamma, dbeta, None, None, None
+        return dx, gid, dgamma, dbeta, None, None, None, None
 
     return type(name, (torch.autograd.Function,),
                 {"__doc__": _join_function.__doc__,
@@ -557,12 +559,13 @@ _HipWhitenJoin = _join_function("_HipWhitenJoin", _HipWhitenMulti)
 _HipBatchNormJoin = _join_function("_HipBatchNormJoin", _HipBatchNormMulti)
 
 
-def batch_norm_multi(x, gamma, beta, running_means, running_vars, cfg):
+def batch_norm_multi(x, gamma, beta, running_means, running_vars, cfg,
+                     stats_acc=None):
     if x.dtype not in (torch.float32, torch.bfloat16):
         from ..ops.functional import BatchNormMulti
-        cfg.pop("stats_acc", None)
         return BatchNormMulti.apply(x, gamma, beta, running_means, running_vars, cfg)
-    return _HipBatchNormMulti.apply(x, gamma, beta, running_means, running_vars, cfg)
+    return _HipBatchNormMulti.apply(x, gamma, beta, running_means, running_vars,
+                                    cfg, stats_acc)
 
 
 class _HipMecLoss(torch.autograd.Function):

@@ -24,6 +24,7 @@ import torch
 import torch.nn as nn
 
 from ..ops.batch_norm import DomainBatchNorm2d
+from ..ops.mfma import conv1x1_routed
 from ..ops.whitening import WhiteningScaleShift
 from ..ops.pooling import MaxPool2dDWT, global_avg_pool
 from .sites import norm_site
@@ -43,23 +44,6 @@ def conv3x3(cin, cout, stride=1):
 
 def conv1x1(cin, cout, stride=1):
     return _conv_cls()(cin, cout, kernel_size=1, stride=stride, bias=False)
-
-
-def _conv_with_stats(conv, x, branches, training):
-    """``(conv(x), stats_acc)`` for a conv feeding the norm site ``branches``.
-
-    An eligible 1x1 stride-1 conv (training, bf16 channels_last on the GPU,
-    BN or g=4 whitening behind it, see ``ops.mfma.conv_stats_route``) runs on
-    the MFMA kernel whose epilogue accumulates that site's raw statistics;
-    ``stats_acc`` then goes to ``norm_site``.  Everything else is the plain
-    conv (for the other 1x1 stride-1 convs on the dense MFMA kernel where its
-    measured table says so, ``ops.mfma.conv1x1_dense``) and ``None``."""
-    from ..ops import mfma
-    route = mfma.conv_stats_route(conv, x, branches, training)
-    if route is None:
-        return mfma.conv1x1_dense(conv, x, training), None
-    kind, g, parts = route
-    return mfma.conv1x1_stats(x, conv.weight, kind, g, parts)
 
 
 def _get(bn_dict: Optional[Dict], key: str):
@@ -157,21 +141,21 @@ class Bottleneck(nn.Module):
         identity = x_id
 
         site1 = [self.bns1, self.bnt1, self.bnt1_aug]
-        out, acc = _conv_with_stats(self.conv1, x, site1, tr)
+        out, acc = conv1x1_routed(self.conv1, x, site1, tr)
         out = norm_site(out, site1, self.gamma1, self.beta1, training=tr,
                         relu=True, stats_acc=acc)
         out = self.conv2(out)
         out = norm_site(out, [self.bns2, self.bnt2, self.bnt2_aug],
                         self.gamma2, self.beta2, training=tr, relu=True)
         site3 = [self.bns3, self.bnt3, self.bnt3_aug]
-        out, acc = _conv_with_stats(self.conv3, out, site3, tr)
+        out, acc = conv1x1_routed(self.conv3, out, site3, tr)
 
         if self.downsample is not None:
             dsite = [self.downsample_bns, self.downsample_bnt,
                      self.downsample_bnt_aug]
             if len(self.downsample) == 1:
-                identity, dacc = _conv_with_stats(self.downsample[0], x,
-                                                  dsite, tr)
+                identity, dacc = conv1x1_routed(self.downsample[0], x,
+                                                dsite, tr)
             else:
                 identity, dacc = self.downsample(x), None
             identity = norm_site(

@@ -364,9 +364,8 @@ def whiten_multi(
     if x.is_cuda:
         from ..kernels import dispatch
         if dispatch.available():
-            if stats_acc is not None:
-                cfg["stats_acc"] = stats_acc
-            return dispatch.whiten_multi(x, gamma, beta, running_means, running_vars, cfg)
+            return dispatch.whiten_multi(x, gamma, beta, running_means,
+                                         running_vars, cfg, stats_acc)
         dispatch.require_or_warn("whiten_multi")
     return WhitenMulti.apply(x, gamma, beta, running_means, running_vars, cfg)
 
@@ -534,9 +533,8 @@ def batch_norm_multi(
     if x.is_cuda:
         from ..kernels import dispatch
         if dispatch.available():
-            if stats_acc is not None:
-                cfg["stats_acc"] = stats_acc
-            return dispatch.batch_norm_multi(x, gamma, beta, running_means, running_vars, cfg)
+            return dispatch.batch_norm_multi(x, gamma, beta, running_means,
+                                             running_vars, cfg, stats_acc)
         dispatch.require_or_warn("batch_norm_multi")
     return BatchNormMulti.apply(x, gamma, beta, running_means, running_vars, cfg)
 
@@ -705,12 +703,10 @@ def norm_join(
             from ..kernels import hip_ops
             cfg = _whiten_cfg(**kw) if kind == "whiten" else _bn_cfg(**kw)
             if hip_ops.join_supported(kind, x, identity, cfg):
-                if stats_acc is not None:
-                    cfg["stats_acc"] = stats_acc
                 fn = hip_ops.whiten_join if kind == "whiten" \
                     else hip_ops.batch_norm_join
                 return fn(x, identity, gamma, beta, running_means,
-                          running_vars, cfg)
+                          running_vars, cfg, stats_acc)
     multi = whiten_multi if kind == "whiten" else batch_norm_multi
     y = add_relu(multi(x, gamma, beta, running_means, running_vars,
                        stats_acc=stats_acc, **kw),

@@ -16,7 +16,8 @@ rounding, 16-byte stores), routed per shape by a measured table.
 """
 from __future__ import annotations
 
-from typing import Optional
+import os
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -84,6 +85,18 @@ class MFMALinear(nn.Linear):
         return F.linear(x, self.weight, self.bias)
 
 
+def _pad_stem_channels(t: torch.Tensor) -> torch.Tensor:
+    """The stem's 3-channel input or weight zero-padded to 4 channels,
+    channels_last, so the kernel's paired-pixel 16-B path applies (NHWC C=4
+    chunks)."""
+    n, _, h, w = t.shape
+    t4 = torch.empty(n, 4, h, w, device=t.device, dtype=t.dtype,
+                     memory_format=torch.channels_last)
+    t4[:, 3] = 0
+    t4[:, :3] = t
+    return t4
+
+
 def conv2d_fwd(x: torch.Tensor, weight: torch.Tensor,
                bias: Optional[torch.Tensor] = None, stride: int = 1,
                padding: int = 0, relu: bool = False) -> torch.Tensor:
@@ -96,18 +109,9 @@ def conv2d_fwd(x: torch.Tensor, weight: torch.Tensor,
     assert x.is_contiguous(memory_format=torch.channels_last) or x.shape[1] == 1
     n, cin, h, w = x.shape
     cout, _, kh, kw = weight.shape
-    if cin == 3:
-        # stem: zero-pad to 4 channels so the kernel's paired-pixel 16-B
-        # path applies (NHWC C=4 chunks); weight padded to match
-        x4 = torch.empty(n, 4, h, w, device=x.device, dtype=x.dtype,
-                         memory_format=torch.channels_last)
-        x4[:, 3] = 0
-        x4[:, :3] = x
-        w4 = torch.empty(cout, 4, kh, kw, device=x.device, dtype=weight.dtype,
-                         memory_format=torch.channels_last)
-        w4[:, 3] = 0
-        w4[:, :3] = weight.detach()
-        x, weight, cin = x4, w4, 4
+    if cin == 3:  # stem; weight padded to match
+        x, weight, cin = _pad_stem_channels(x), \
+            _pad_stem_channels(weight.detach()), 4
     p = (h + 2 * padding - kh) // stride + 1
     q = (w + 2 * padding - kw) // stride + 1
     out = torch.empty(n, cout, p, q, device=x.device, dtype=torch.bfloat16,
@@ -246,18 +250,10 @@ def conv2d_fused_fwd(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
             return Fdwt.add_relu(y, residual) if relu else y + residual
         return y.relu_() if relu else y
 
-    if cin == 3:
-        # stem: zero-pad to 4 channels so the kernel's paired-pixel 16-B
-        # path applies (NHWC C=4 chunks)
-        x4 = torch.empty(n, 4, h, w, device=x.device, dtype=x.dtype,
-                         memory_format=torch.channels_last)
-        x4[:, 3] = 0
-        x4[:, :3] = x
-        x, cin = x4, 4
+    if cin == 3:  # stem; a weight the caller padded already stays as it is
+        x, cin = _pad_stem_channels(x), 4
         if wcin == 3:
-            w4 = weight.new_zeros(cout, 4, kh, kw)
-            w4[:, :3] = weight.detach()
-            weight = w4
+            weight = _pad_stem_channels(weight.detach())
     wgt = weight.detach()
     if not _is_nhwc(wgt):
         wgt = wgt.contiguous(memory_format=torch.channels_last)
@@ -282,7 +278,6 @@ _STATS_KINDS = {"bn": 0, "whiten": 1}
 def fused_conv_stats_enabled() -> bool:
     """``DWT_AMD_FUSED_CONV_STATS=0`` sends every 1x1 conv back to the library
     forward + stand-alone stats kernel.  Read on every call."""
-    import os
     return os.environ.get("DWT_AMD_FUSED_CONV_STATS", "1") != "0"
 
 
@@ -309,53 +304,9 @@ def conv_stats_shape_ok(m: int, cin: int, cout: int) -> bool:
 _ROUTE_MIN_C = 128
 
 
-def conv_stats_route(conv, x: torch.Tensor, branches, training: bool):
-    """``(kind, g, parts)`` when ``conv`` followed by the norm site
-    ``branches`` can run as :func:`conv1x1_stats` on ``x``, else ``None``."""
-    if not training or not fused_conv_stats_enabled():
-        return None
-    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
-            and x.is_contiguous(memory_format=torch.channels_last)):
-        return None
-    if type(conv) is not nn.Conv2d or conv.bias is not None \
-            or conv.kernel_size != (1, 1) or conv.stride != (1, 1) \
-            or conv.padding != (0, 0) or conv.dilation != (1, 1) \
-            or conv.groups != 1 or conv.weight.dtype != torch.bfloat16:
-        return None
-    from ..kernels import dispatch
-    if not dispatch.available():
-        return None
-    from ..kernels import hip_ops
-    from .whitening import WhiteningScaleShift, WTransform2d
-    from .batch_norm import _DomainBatchNorm
-    n, cin, h, w = x.shape
-    cout = conv.out_channels
-    parts = len(branches)
-    first = branches[0]
-    if isinstance(first, (WhiteningScaleShift, WTransform2d)):
-        wh = first.wh if isinstance(first, WhiteningScaleShift) else first
-        g = cout // wh.num_groups
-        if g != 4 or not hip_ops.whiten_cl_supported(cout, g):
-            return None
-        kind = "whiten"
-    elif isinstance(first, _DomainBatchNorm):
-        if not hip_ops._bn_cl_supported(cout):
-            return None
-        kind, g = "bn", 0
-    else:
-        return None
-    if h * w == 1 or cout == 1:
-        return None  # channels_last is ambiguous there; keep the old path
-    if cin % 8 or cout % 8 or n % parts \
-            or (n // parts * h * w) % STATS_TILE_M:
-        return None
-    if not conv_stats_shape_ok(n * h * w, cin, cout):
-        return None
-    return kind, g, parts
-
-
 # ----------------------------------------------------------------------------
-# Routing of the 1x1 stride-1 convs to the dense MFMA kernel
+# Routing of the 1x1 stride-1 convs in training: stats-epilogue, dense or
+# library forward; dense or library data gradient
 # ----------------------------------------------------------------------------
 
 # ``(pass, Cin, Cout)`` of the conv, pass in {"fwd", "dgrad"}: the shapes where
@@ -379,8 +330,8 @@ _DENSE_ROUTE = {
 
 def dense_route_enabled() -> bool:
     """``DWT_AMD_DENSE_ROUTE=0`` keeps every 1x1 dgrad and the layer-1 1x1
-    forwards on the library.  Read on every call."""
-    import os
+    forwards on the library.  Read when a conv is planned, in its forward;
+    the backward follows the plan made then."""
     return os.environ.get("DWT_AMD_DENSE_ROUTE", "1") != "0"
 
 
@@ -390,118 +341,173 @@ def dense_route_ok(which: str, cin: int, cout: int) -> bool:
     return (which, cin, cout) in _DENSE_ROUTE
 
 
-def _dense_kernel_usable(x: torch.Tensor, weight: torch.Tensor) -> bool:
+def mfma_1x1_usable(x: torch.Tensor, weight: torch.Tensor, conv=None) -> bool:
+    """Whether the MFMA 1x1 kernels (stats-epilogue and dense forward, dense
+    data gradient) can run this conv on this input: a 1x1 bf16 ``weight``,
+    where given the plain stride-1 bias-free ``nn.Conv2d`` it belongs to
+    (``MFMAConv2d`` has its own path), on CUDA bf16 channels_last ``x``, both
+    channel counts a multiple of 8, and the extension loaded."""
+    if conv is not None and (
+            type(conv) is not nn.Conv2d or conv.bias is not None
+            or conv.kernel_size != (1, 1) or conv.stride != (1, 1)
+            or conv.padding != (0, 0) or conv.dilation != (1, 1)
+            or conv.groups != 1):
+        return False
     if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.bfloat16
             and weight.dtype == torch.bfloat16 and weight.dim() == 4
-            and tuple(weight.shape[2:]) == (1, 1)
+            and tuple(weight.shape[1:]) == (x.shape[1], 1, 1)
             and x.is_contiguous(memory_format=torch.channels_last)):
         return False
     n, cin, h, w = x.shape
-    cout = weight.shape[0]
-    if h * w == 1 or cin % 8 or cout % 8 or weight.shape[1] != cin:
+    # H*W == 1: channels_last is ambiguous there; keep the library path
+    if h * w == 1 or cin % 8 or weight.shape[0] % 8:
         return False
     from ..kernels import dispatch
     return dispatch.available()
 
 
-def _conv1x1_backward(fn, dout, x, weight, need_dx):
-    """``(dx, dw)`` of a 1x1 stride-1 bias-free conv.  dx runs on the dense
-    kernel (dy @ W, with a per-call transposed copy of W) where the table says
-    so, dw then comes from the library alone; otherwise both are the library's,
-    exactly as before.  ``fn.dgrad_calls`` counts the routed ones."""
-    cout, cin = weight.shape[0], weight.shape[1]
-    if need_dx and dense_route_enabled() and dense_route_ok("dgrad", cin, cout) \
-            and _dense_kernel_usable(x, weight):
-        dout = dout.contiguous(memory_format=torch.channels_last)
-        dx = conv2d_dgrad(dout, weight.detach(), x.shape)
-        fn.dgrad_calls += 1
-        _, dw, _ = torch.ops.aten.convolution_backward(
-            dout, x, weight, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
-            [False, True, False])
-        return dx, dw
-    dx, dw, _ = torch.ops.aten.convolution_backward(
-        dout, x, weight, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
-        [need_dx, True, False])
-    return dx, dw
+class Conv1x1Plan(NamedTuple):
+    """Which kernels one 1x1 stride-1 conv of a training step runs on."""
+    fwd: str                # "stats", "dense" or "library"
+    dgrad: str              # "dense" or "library"
+    kind: Optional[str]     # of the norm site behind the conv: "bn", "whiten"
+    g: int                  # that site's whitening group size (0 for BN)
+    parts: int              # its domain branches
+
+
+def _stats_rows_ok(n: int, h: int, w: int, parts: int) -> bool:
+    """Each branch's rows are a whole number of the stats kernel's M tiles."""
+    return parts >= 1 and n % parts == 0 \
+        and (n // parts * h * w) % STATS_TILE_M == 0
+
+
+def plan_conv1x1(n: int, cin: int, h: int, w: int, cout: int,
+                 kind: Optional[str], g: int, parts: int) -> Conv1x1Plan:
+    """The plan for a conv :func:`mfma_1x1_usable` accepts, from its sizes,
+    the norm site behind it (``kind`` None: a site the stats kernel does not
+    serve) and the two switches.  No tensors, no device: the measured tables
+    and the NHWC norm kernels' channel ranges decide."""
+    from ..kernels import hip_ops
+    dense = dense_route_enabled()
+    site_ok = (kind == "whiten" and g == 4
+               and hip_ops.whiten_cl_supported(cout, g)) \
+        or (kind == "bn" and hip_ops.bn_cl_supported(cout))
+    if fused_conv_stats_enabled() and site_ok \
+            and _stats_rows_ok(n, h, w, parts) \
+            and conv_stats_shape_ok(n * h * w, cin, cout):
+        fwd = "stats"
+    elif dense and dense_route_ok("fwd", cin, cout):
+        fwd = "dense"
+    else:
+        fwd = "library"
+    dgrad = "dense" if dense and dense_route_ok("dgrad", cin, cout) \
+        else "library"
+    return Conv1x1Plan(fwd, dgrad, kind, g, parts)
+
+
+def _site_kind(branches, cout: int):
+    """``(kind, g)`` of the norm site ``branches`` for :func:`plan_conv1x1`."""
+    from .whitening import WhiteningScaleShift, WTransform2d
+    from .batch_norm import _DomainBatchNorm
+    first = branches[0]
+    if isinstance(first, (WhiteningScaleShift, WTransform2d)):
+        wh = first.wh if isinstance(first, WhiteningScaleShift) else first
+        return "whiten", cout // wh.num_groups
+    if isinstance(first, _DomainBatchNorm):
+        return "bn", 0
+    return None, 0
 
 
 class _Conv1x1Fn(torch.autograd.Function):
-    """A 1x1 stride-1 bias-free conv whose forward and data gradient run on
-    the dense MFMA kernel where the measured table says so, on the library
-    otherwise (always without the extension)."""
+    """A 1x1 stride-1 bias-free conv run as its :class:`Conv1x1Plan` says.
+    Forward: the persistent MFMA GEMM with the stats epilogue (then ``acc`` is
+    the raw-sums accumulator, else None), the dense MFMA kernel, or the
+    library.  Backward: dx on the dense kernel (dy @ W, with a per-call
+    transposed copy of W) and dw from the library alone, or both from the
+    library.  The plan is fixed here in the forward; the backward re-reads no
+    switch.  On CPU tensors every plan runs as library/library: the kernels
+    need the device."""
 
-    fwd_calls = 0     # forwards on the dense kernel
-    dgrad_calls = 0   # data gradients on the dense kernel
+    stats_calls = 0         # forwards on the stats-epilogue kernel
+    dense_fwd_calls = 0     # forwards on the dense kernel
+    dense_dgrad_calls = 0   # data gradients on the dense kernel
 
     @staticmethod
-    def forward(ctx, x, weight):
-        cout, cin = weight.shape[0], weight.shape[1]
-        if dense_route_enabled() and dense_route_ok("fwd", cin, cout) \
-                and _dense_kernel_usable(x, weight):
+    def forward(ctx, x, weight, plan, max_workgroups=0):
+        if not x.is_cuda:
+            # a hand-made plan on CPU tensors (the plumbing tests): the
+            # kernels need the device, so both passes are the library's
+            plan = plan._replace(fwd="library", dgrad="library")
+        acc = None
+        if plan.fwd == "stats":
+            n, cin, h, w = x.shape
+            cout = weight.shape[0]
+            out = torch.empty(n, cout, h, w, device=x.device,
+                              dtype=torch.bfloat16,
+                              memory_format=torch.channels_last)
+            acc = torch.zeros(stats_acc_numel(plan.kind, cout, plan.parts),
+                              device=x.device, dtype=torch.float32)
+            wgt = weight.detach().reshape(cout, cin).contiguous()
+            _ext().conv1x1_stats(x, wgt, out, acc, _STATS_KINDS[plan.kind],
+                                 plan.g, plan.parts, max_workgroups)
+            _Conv1x1Fn.stats_calls += 1
+            ctx.mark_non_differentiable(acc)
+        elif plan.fwd == "dense":
             out = conv2d_fwd(x, weight.detach())
-            _Conv1x1Fn.fwd_calls += 1
+            _Conv1x1Fn.dense_fwd_calls += 1
         else:
             out = F.conv2d(x, weight)
         ctx.save_for_backward(x, weight)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        x, weight = ctx.saved_tensors
-        dx, dw = _conv1x1_backward(_Conv1x1Fn, dout, x, weight,
-                                   ctx.needs_input_grad[0])
-        return dx, dw
-
-
-def conv1x1_dense(conv, x: torch.Tensor, training: bool) -> torch.Tensor:
-    """``conv(x)`` for the 1x1 stride-1 bias-free convs that do not take the
-    stats route: in training, through :class:`_Conv1x1Fn` when the dense
-    kernel can run and the table routes the forward or the data gradient of
-    this shape, else the module's own forward."""
-    if not training or not dense_route_enabled() \
-            or type(conv) is not nn.Conv2d \
-            or conv.bias is not None or conv.kernel_size != (1, 1) \
-            or conv.stride != (1, 1) or conv.padding != (0, 0) \
-            or conv.dilation != (1, 1) or conv.groups != 1:
-        return conv(x)
-    cin, cout = conv.in_channels, conv.out_channels
-    if not (dense_route_ok("fwd", cin, cout) or dense_route_ok("dgrad", cin, cout)):
-        return conv(x)
-    if not _dense_kernel_usable(x, conv.weight):
-        return conv(x)
-    return _Conv1x1Fn.apply(x, conv.weight)
-
-
-class _Conv1x1StatsFn(torch.autograd.Function):
-    """Forward: the persistent MFMA GEMM with the stats epilogue.  Backward:
-    the data gradient on the dense MFMA kernel where the table routes it, the
-    rest on the library (see :func:`_conv1x1_backward`)."""
-
-    calls = 0   # forward launches (tests assert the fused path really ran)
-    dgrad_calls = 0   # data gradients on the dense kernel
-
-    @staticmethod
-    def forward(ctx, x, weight, kind, g, parts, max_workgroups):
-        n, cin, h, w = x.shape
-        cout = weight.shape[0]
-        out = torch.empty(n, cout, h, w, device=x.device, dtype=torch.bfloat16,
-                          memory_format=torch.channels_last)
-        acc = torch.zeros(stats_acc_numel(kind, cout, parts), device=x.device,
-                          dtype=torch.float32)
-        wgt = weight.detach().reshape(cout, cin).contiguous()
-        _ext().conv1x1_stats(x, wgt, out, acc, _STATS_KINDS[kind], g, parts,
-                             max_workgroups)
-        _Conv1x1StatsFn.calls += 1
-        ctx.save_for_backward(x, weight)
-        ctx.mark_non_differentiable(acc)
+        ctx.dense_dgrad = plan.dgrad == "dense"
         return out, acc
 
     @staticmethod
     def backward(ctx, dout, _dacc):
         x, weight = ctx.saved_tensors
-        dx, dw = _conv1x1_backward(_Conv1x1StatsFn, dout, x, weight,
-                                   ctx.needs_input_grad[0])
-        return dx, dw, None, None, None, None
+        need_dx = ctx.needs_input_grad[0]
+        dense = ctx.dense_dgrad and need_dx
+        if dense:
+            dout = dout.contiguous(memory_format=torch.channels_last)
+            dense_dx = conv2d_dgrad(dout, weight.detach(), x.shape)
+            _Conv1x1Fn.dense_dgrad_calls += 1
+        dx, dw, _ = torch.ops.aten.convolution_backward(
+            dout, x, weight, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
+            [need_dx and not dense, True, False])
+        return dense_dx if dense else dx, dw, None, None
+
+
+def _plan_of(conv, x: torch.Tensor, branches, training: bool):
+    """The plan of ``conv`` on ``x`` in front of the norm site ``branches``,
+    or None where the MFMA 1x1 kernels cannot run it (or not training)."""
+    if not training or not mfma_1x1_usable(x, conv.weight, conv):
+        return None
+    n, cin, h, w = x.shape
+    cout = conv.out_channels
+    return plan_conv1x1(n, cin, h, w, cout, *_site_kind(branches, cout),
+                        len(branches))
+
+
+def conv1x1_routed(conv, x: torch.Tensor, branches, training: bool):
+    """``(conv(x), stats_acc)`` for a conv feeding the norm site ``branches``:
+    the model's one entry to the routing.  In training, a conv the MFMA 1x1
+    kernels can run goes through :class:`_Conv1x1Fn` with its plan, and
+    ``stats_acc`` (not None after a stats-epilogue forward) goes to
+    ``norm_site``.  Everything else, an all-library plan included, is the
+    module's own forward and ``None``."""
+    plan = _plan_of(conv, x, branches, training)
+    if plan is None or (plan.fwd == "library" and plan.dgrad == "library"):
+        return conv(x), None
+    return _Conv1x1Fn.apply(x, conv.weight, plan)
+
+
+def conv_stats_route(conv, x: torch.Tensor, branches, training: bool):
+    """``(kind, g, parts)`` when :func:`conv1x1_routed` would run ``conv`` on
+    the stats-epilogue forward, else ``None``: the question without the conv,
+    answered by the same plan."""
+    plan = _plan_of(conv, x, branches, training)
+    if plan is None or plan.fwd != "stats":
+        return None
+    return plan.kind, plan.g, plan.parts
 
 
 def conv1x1_stats(x: torch.Tensor, weight: torch.Tensor, kind: str,
@@ -516,28 +522,16 @@ def conv1x1_stats(x: torch.Tensor, weight: torch.Tensor, kind: str,
     None)``: the norm site then takes its own statistics.
     """
     assert kind in _STATS_KINDS, kind
-    if not _conv1x1_stats_applies(x, weight, kind, g, parts):
+    if (kind == "whiten" and g != 4) or not mfma_1x1_usable(x, weight):
         return F.conv2d(x, weight), None
-    return _Conv1x1StatsFn.apply(x, weight, kind, g, parts, max_workgroups)
-
-
-def _conv1x1_stats_applies(x, weight, kind, g, parts) -> bool:
-    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.bfloat16
-            and weight.dtype == torch.bfloat16
-            and x.is_contiguous(memory_format=torch.channels_last)):
-        return False
-    if weight.dim() != 4 or weight.shape[2:] != (1, 1) \
-            or weight.shape[1] != x.shape[1]:
-        return False
     n, cin, h, w = x.shape
-    cout = weight.shape[0]
-    if kind == "whiten" and g != 4:
-        return False
-    if cin % 8 or cout % 8 or parts < 1 or n % parts \
-            or (n // parts * h * w) % STATS_TILE_M:
-        return False
-    from ..kernels import dispatch
-    return dispatch.available()
+    if not _stats_rows_ok(n, h, w, parts):
+        return F.conv2d(x, weight), None
+    # the stats forward whatever its switch and shape table say; the data
+    # gradient as planned
+    plan = plan_conv1x1(n, cin, h, w, weight.shape[0], kind, g, parts)
+    return _Conv1x1Fn.apply(x, weight, plan._replace(fwd="stats"),
+                            max_workgroups)
 
 
 def conv2d_dgrad(dy: torch.Tensor, weight: torch.Tensor, in_shape,
@@ -572,7 +566,6 @@ class _MFMAConv2dFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        import os
         x, weight = ctx.saved_tensors
         stride, padding, has_bias = ctx.meta
         dout = dout.contiguous(memory_format=torch.channels_last)

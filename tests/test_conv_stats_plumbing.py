@@ -9,7 +9,8 @@ from dwt_amd.models import Bottleneck, ResNetDWT
 from dwt_amd.models.sites import norm_site
 from dwt_amd.ops import oracle
 from dwt_amd.ops.batch_norm import DomainBatchNorm2d
-from dwt_amd.ops.mfma import conv1x1_stats, conv_stats_route, stats_acc_numel
+from dwt_amd.ops.mfma import (conv1x1_routed, conv1x1_stats, conv_stats_route,
+                              stats_acc_numel)
 from dwt_amd.ops.oracle import stats_acc_reference
 from dwt_amd.ops.whitening import WhiteningScaleShift
 
@@ -43,6 +44,11 @@ def test_route_and_wrapper_fall_back_on_cpu():
         memory_format=torch.channels_last)
     branches = [DomainBatchNorm2d(64, affine=False) for _ in range(PARTS)]
     assert conv_stats_route(conv, x, branches, True) is None
+    out, acc = conv1x1_routed(conv, x, branches, True)
+    assert acc is None
+    assert torch.equal(out, conv(x))
+    # the module's own forward: no routing Function on the graph
+    assert "Conv1x1Fn" not in type(out.grad_fn).__name__
     out, acc = conv1x1_stats(x, conv.weight, "bn", G, PARTS)
     assert acc is None
     assert torch.equal(out, conv(x))

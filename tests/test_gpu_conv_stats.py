@@ -107,11 +107,11 @@ def test_conv_out_and_acc(dev, shape, kind, max_wg):
 @pytest.mark.parametrize("kind", KINDS)
 def test_unaligned_falls_back(dev, kind):
     """b*h*w = 18 rows per branch: no multiple of the 128-row tile."""
-    from dwt_amd.ops.mfma import _Conv1x1StatsFn, conv1x1_stats
+    from dwt_amd.ops.mfma import _Conv1x1Fn, conv1x1_stats
     x, wt, ref = _conv_case(UNALIGNED)
-    before = _Conv1x1StatsFn.calls
+    before = _Conv1x1Fn.stats_calls
     out, acc = conv1x1_stats(x, wt, kind, G, PARTS)
-    assert _Conv1x1StatsFn.calls == before
+    assert _Conv1x1Fn.stats_calls == before
     assert acc is None
     assert _rel_err(out, ref) < 0.05
     # the site behind it computes its own statistics
@@ -298,11 +298,11 @@ def test_bottleneck_switch(dev, style, monkeypatch):
     monkeypatch.setattr(mfma, "conv_stats_shape_ok", lambda m, cin, cout: True)
     expect = 3 if style == "layer1" else 2
 
-    before = mfma._Conv1x1StatsFn.calls
+    before = mfma._Conv1x1Fn.stats_calls
     y_off, dx_off, g_off = _block_step(blk, x, wl, False, monkeypatch)
-    assert mfma._Conv1x1StatsFn.calls == before
+    assert mfma._Conv1x1Fn.stats_calls == before
     y_on, dx_on, g_on = _block_step(blk, x, wl, True, monkeypatch)
-    assert mfma._Conv1x1StatsFn.calls == before + expect  # no silent fallback
+    assert mfma._Conv1x1Fn.stats_calls == before + expect  # no silent fallback
 
     print(f"{style}: y {_rel_err(y_on, y_off):.3g} dx {_rel_err(dx_on, dx_off):.3g}")
     assert _rel_err(y_on, y_off) < 0.05

@@ -264,8 +264,9 @@ def _block_step(blk, x, wl, on, monkeypatch):
 
 
 def _counters(mfma):
-    return (mfma._Conv1x1Fn.fwd_calls, mfma._Conv1x1Fn.dgrad_calls,
-            mfma._Conv1x1StatsFn.calls, mfma._Conv1x1StatsFn.dgrad_calls)
+    """(dense forwards, stats forwards, dense data gradients)"""
+    fn = mfma._Conv1x1Fn
+    return (fn.dense_fwd_calls, fn.stats_calls, fn.dense_dgrad_calls)
 
 
 @pytest.mark.parametrize("style", ["layer1", "layer2"])
@@ -282,19 +283,19 @@ def test_bottleneck_dense_route(ext, style, monkeypatch):
     y_off, dx_off, g_off = _block_step(blk, x, wl, False, monkeypatch)
     c1 = _counters(mfma)
     g1 = ext.dense_glds_launches()
-    assert (c1[0], c1[1], c1[3]) == (c0[0], c0[1], c0[3]), "switch off still routed"
+    assert (c1[0], c1[2]) == (c0[0], c0[2]), "switch off still routed"
     y_on, dx_on, g_on = _block_step(blk, x, wl, True, monkeypatch)
     c2 = _counters(mfma)
     g2 = ext.dense_glds_launches()
     d = tuple(b - a for a, b in zip(c1, c2))
     if style == "layer1":
         # conv1, conv3 and the stride-1 downsample: the table of the stats
-        # route keeps all three on the plain forward, so they are _Conv1x1Fn
-        assert d == (3, 3, 0, 0), d
+        # route keeps all three on the plain forward, so they are dense
+        assert d == (3, 0, 3), d
         assert g1 - g0 == 0 and g2 - g1 == 6      # no silent fallback
     else:
         # conv1 and conv3 run the fused stats forward; their dgrads route
-        assert d == (0, 0, 2, 2), d
+        assert d == (0, 2, 2), d
         assert g1 - g0 == 2 and g2 - g1 == 4
 
     print(f"{style}: y {_rel_err(y_on, y_off):.3g} dx {_rel_err(dx_on, dx_off):.3g}")
@@ -305,3 +306,31 @@ def test_bottleneck_dense_route(ext, style, monkeypatch):
         err = _rel_err(g_on[name], g_off[name])
         print(f"  {name}: {err:.3g}")
         assert err < 0.05, (name, err)
+
+
+def test_whole_model_routes_by_the_tables(dev, monkeypatch):
+    """The committed tables, unpatched, on a whole model: one forward and
+    backward of ResNetDWT [1, 1, 1, 1] on 96x3x64x64 (32 images per branch).
+    Rows per branch are 8192, 2048, 512 and 128 in layers 1-4, the smallest
+    sizes at which every stage still meets the stats kernel's 128-row tile.
+
+    Layer 1's conv1, conv3 and stride-1 downsample take the dense forward
+    (3); conv1 and conv3 of layers 2-4 the stats forward (6); all nine take
+    the dense data gradient.  The stride-2 downsamples are the module's."""
+    from dwt_amd.models import Bottleneck, ResNetDWT
+    from dwt_amd.ops import mfma
+    monkeypatch.delenv("DWT_AMD_DENSE_ROUTE", raising=False)
+    monkeypatch.delenv("DWT_AMD_FUSED_CONV_STATS", raising=False)
+    torch.manual_seed(7)
+    model = ResNetDWT(Bottleneck, [1, 1, 1, 1], None, num_classes=5)
+    model = model.to(dev).to(torch.bfloat16) \
+        .to(memory_format=torch.channels_last).train()
+    x = torch.randn(PARTS * 32, 3, 64, 64, device=dev, dtype=torch.bfloat16) \
+        .contiguous(memory_format=torch.channels_last)
+    c0 = _counters(mfma)
+    out = model(x)
+    out.float().square().sum().backward()
+    torch.cuda.synchronize()
+    d = tuple(b - a for a, b in zip(c0, _counters(mfma)))
+    assert d == (3, 6, 9), d
+    assert torch.isfinite(out).all()

@@ -154,9 +154,12 @@ def test_whiten_handed_over_stats(rec, right_size):
     x, gamma, beta = _whiten_inputs(c, True)
     numel = parts * (c // g) * (g + g * g)
     handed = torch.zeros(numel if right_size else numel - 1)
-    cfg = _whiten_cfg(parts, c // g, stats_acc=handed)
-    hip_ops._HipWhitenMulti.apply(x, gamma, beta, None, None, cfg)
-    assert "stats_acc" not in cfg
+    cfg = _whiten_cfg(parts, c // g)
+    cfg_before = dict(cfg)
+    hip_ops._HipWhitenMulti.apply(x, gamma, beta, None, None, cfg, handed)
+    # the accumulator is an argument: cfg is left as it was and holds no tensor
+    assert cfg == cfg_before
+    assert not any(isinstance(v, torch.Tensor) for v in cfg.values())
     tail = ["whiten_stats_final", "matfn_chol_fwd", "whiten_apply_cl"]
     acc = rec.args("whiten_stats_final")[0]
     if right_size:
@@ -245,6 +248,30 @@ def test_bn_route(rec, shape, cl, sfx):
             == [parts * c, parts * c, parts * 2 * c]
         assert rec.args("bn_bwd_apply")[-2] == cnt
     assert x.grad.shape == x.shape and gamma.grad.shape == gamma.shape
+
+
+@pytest.mark.parametrize("join", [False, True], ids=["plain", "join"])
+def test_bn_handed_over_stats(rec, join):
+    """As test_whiten_handed_over_stats; the join Function passes the
+    accumulator through to the site's forward."""
+    parts, c = 3, 128
+    x, gamma, beta = _bn_inputs((6, c, 5, 7), True)
+    handed = torch.zeros(parts * 2 * c)
+    cfg = _bn_cfg(parts)
+    cfg_before = dict(cfg)
+    if join:
+        identity = torch.randn(6, c, 5, 7) \
+            .contiguous(memory_format=torch.channels_last)
+        hip_ops.batch_norm_join(x, identity, gamma, beta, None, None, cfg,
+                                handed)
+    else:
+        hip_ops._HipBatchNormMulti.apply(x, gamma, beta, None, None, cfg,
+                                         handed)
+    assert cfg == cfg_before
+    assert not any(isinstance(v, torch.Tensor) for v in cfg.values())
+    assert rec.names() == ["bn_stats_final",
+                           "bn_apply_res_cl" if join else "bn_apply_cl"]
+    assert rec.args("bn_stats_final")[0].data_ptr() == handed.data_ptr()
 
 
 def test_bn_route_one_part(rec):
